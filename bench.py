@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload chamfer|fps|ball_group]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload chamfer|fps|ball_group] [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[1]: Chamfer forward+backward, B=32 (per GPU), N=M=16384,
 C=3, fp32, synthetic area-uniform unit-sphere clouds (two input sets alternating), through the public
@@ -30,6 +30,9 @@ The JSON line also carries
   other_ops_ms  three_nn, three_interpolate, knn_points (K = 1, 8, 16), labeled Chamfer at the shapes of DESIGN.md 5.6
   cpu_baseline  the CPU oracle (a port of the reference semantics; the reference has no CPU
                 path) timed on this host's cores on a bounded sample of the same workload
+  host_cpus     the CPUs the GPU timings ran on: the process keeps to one L3 domain on the GPU's NUMA
+                node (pin_to_one_l3_domain), the CPU leg alone uses all it may; what the eager step
+                costs with the calling thread in another domain is launch_modes "eager_threads_apart"
 """
 import argparse
 import json
@@ -77,6 +80,61 @@ def _pmc_traffic_c2():
 
 
 
+ALL_CPUS = None     # the CPUs the process may run on, before pin_to_one_l3_domain narrowed them
+APART_CPUS = None   # an L3 domain away from the one kept (another NUMA node where there is one): eager_threads_apart
+
+
+def _set_affinity(cpus):
+    """every thread of the process (threads started later inherit their parent's)"""
+    for tid in os.listdir("/proc/self/task"):
+        try:
+            os.sched_setaffinity(int(tid), cpus)
+        except OSError:
+            pass    # (a thread that has just ended)
+
+
+def pin_to_one_l3_domain(device):
+    """Keep the process on the CPUs that share one L3 cache, on the GPU's NUMA node: its threads and the ones started
+    later (the autograd engine's device thread).  The eager step hands its backward to the engine's device thread and
+    waits for it; left to the scheduler the two threads land anywhere on the host, and whether they share an L3 domain
+    changes from one process to the next: ms_per_step of one build spread over 0.072-0.098 ms across processes on a
+    two-socket host with 16 L3 domains, 0.0720-0.0722 ms held to one domain -- too wide to compare two builds.  What
+    the threads cost apart is still measured, beside the headline: launch_modes_ms_per_step["eager_threads_apart"].
+    The domain is the one the process runs in where that is on the GPU's node, else one of that node's picked by the
+    CPU it runs on, so that concurrent processes stay spread.
+    -> {"cpus", "numa_node", "apart_cpus"} for the result line, or None where the topology cannot be read or the
+    domain would hold fewer than 4 CPUs (nothing is changed then)."""
+    global ALL_CPUS, APART_CPUS
+    try:
+        allowed = os.sched_getaffinity(0)
+        cpu = int(open("/proc/self/stat").read().rsplit(")", 1)[1].split()[36])   # field 39: the CPU it last ran on
+        p = torch.cuda.get_device_properties(device)
+        gpu_node = int(open("/sys/bus/pci/devices/%04x:%02x:%02x.0/numa_node"
+                            % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)).read())
+        domains, node_of = {}, {}
+        for c in sorted(allowed):
+            key = open("/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list" % c).read().strip()
+            domains.setdefault(key, set()).add(c)
+            nodes = [f for f in os.listdir("/sys/devices/system/cpu/cpu%d" % c) if f.startswith("node")]
+            node_of[key] = int(nodes[0][4:]) if nodes else -1
+    except (OSError, ValueError, IndexError, AttributeError, RuntimeError):
+        return None
+    here = [k for k, v in domains.items() if cpu in v]
+    near = sorted((k for k in domains if gpu_node < 0 or node_of[k] == gpu_node), key=lambda k: min(domains[k]))
+    if not near:
+        return None
+    key = here[0] if here and here[0] in near else near[cpu % len(near)]
+    keep = domains[key]
+    if len(keep) < 4:
+        return None
+    others = sorted((k for k in domains if k != key), key=lambda k: (node_of[k] == node_of[key], min(domains[k])))
+    ALL_CPUS, APART_CPUS = allowed, (domains[others[0]] if others else None)
+    if keep != allowed:
+        _set_affinity(keep)
+    return {"cpus": sorted(keep), "numa_node": node_of[key],
+            "apart_cpus": sorted(APART_CPUS) if APART_CPUS else None}
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -100,7 +158,52 @@ def parse():
     ap.add_argument("--no-extras", action="store_true",
                     help="chamfer: skip the short runs of the other workloads (fps, ball_group) and distributions")
     ap.add_argument("--with-backward", action="store_true", help="ball_group: also time group_points_grad")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: larger outputs as a fixed, seeded sample); with "
+                         "--gpus N, rank 0's shard of the batch")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: bytes of array data written at most, all arrays together
+# what a caller of the timed Chamfer step receives: nndistance's four outputs and the two coordinate gradients
+CHAMFER_OUTPUTS = ("dist1", "dist2", "idx1", "idx2", "grad_xyz1", "grad_xyz2")
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor: what the timed path returned in its last step) as
+    out_dir/<name>.npy.  Floating tensors as float32 (float64 stays float64); integer ones as float32 where every value
+    is exact in it, else float64.  When the set is larger than DUMP_BYTES every array is cut to the same fraction of its
+    elements, a stratified sample of its flattened positions fixed by its size and a seed, so that two runs with the
+    same arguments write the same positions (1-D).  -> {name: {"shape", "written"}} for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    plan = []
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype == torch.float64:
+            dt = torch.float64
+        elif t.is_floating_point() or t.numel() == 0 or int(t.abs().max()) < 2 ** 24:
+            dt = torch.float32
+        else:
+            dt = torch.float64
+        plan.append((name, t, dt))
+    total = sum(t.numel() * (8 if dt == torch.float64 else 4) for _, t, dt in plan)
+    budget = DUMP_BYTES - 256 * len(plan)          # (room for the .npy headers)
+    frac = budget / total if total > budget else 1.0
+    info = {}
+    for name, t, dt in plan:
+        n = t.numel()
+        k = n if frac == 1.0 else max(1, int(n * frac))
+        if k < n:
+            edges = np.arange(k + 1, dtype=np.int64) * n // k
+            pos = edges[:-1] + (np.random.default_rng(0).random(k) * np.diff(edges)).astype(np.int64)
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(dt).cpu().numpy())
+        info[name] = {"shape": list(arrays[name].shape), "written": k}
+    return info
 
 
 def init_dist(args):
@@ -327,6 +430,8 @@ def bench_chamfer(args, dist, world, rank, device):
         exchange = PackedShardGather(B, N, M, device)
     pending = []        # slot of the previous gathered step
     counter = [0]
+    last = []           # what the latest step returned to its caller (--dump-outputs): CHAMFER_OUTPUTS, in that order;
+    #                     let go at the start of the next step, so that its buffers are free for the next step's outputs
     gather_every = max(1, args.gather_every)
 
     def gathers():
@@ -349,6 +454,7 @@ def bench_chamfer(args, dist, world, rank, device):
     def eager_step():
         """the operator as a user calls it: torch.autograd.Function forward, autograd backward; with an exchange, the
         search writes its distances straight into the exchange's slot (PackedShardGather.forward)"""
+        del last[:]
         x1, x2 = sets[counter[0] & 1]
         counter[0] += 1
         x1.grad = None
@@ -360,6 +466,7 @@ def bench_chamfer(args, dist, world, rank, device):
         else:
             d1, d2, i1, i2 = nndistance(x1, x2)
         torch.autograd.backward([d1, d2], [g1, g2])
+        last[:] = (d1, d2, i1, i2, x1.grad, x2.grad)
 
     def drain():
         if exchange is not None:
@@ -409,8 +516,10 @@ def bench_chamfer(args, dist, world, rank, device):
             slot, v1, v2 = exchange.begin()
             ext_losses.nmdistance_forward(sx1, sx2, v1, v2, oi1, oi2)
             pending.append(exchange.launch_in_place(slot, oi1, oi2))
+            last[:] = (v1, v2, oi1, oi2, ogx1, ogx2)
         else:
             ext_losses.nmdistance_forward(sx1, sx2, od1, od2, oi1, oi2)
+            last[:] = (od1, od2, oi1, oi2, ogx1, ogx2)
         ext_losses.nmdistance_backward(sx1, sx2, ogx1, ogx2, g1, g2, oi1, oi2)
 
     # hipGraph replay of one step (pytorch_points_amd/graphs.py; static inputs: set A)
@@ -436,8 +545,9 @@ def bench_chamfer(args, dist, world, rank, device):
 
     def graph_step():
         counter[0] += 1
-        d1, d2, i1, i2, _, _ = gstep.replay()
+        d1, d2, i1, i2, gx1, gx2 = gstep.replay()
         maybe_exchange(d1, d2, i1, i2)
+        last[:] = (d1, d2, i1, i2, gx1, gx2)
 
     # ---- the timed region: the autograd operator (eager) unless another issue mode is asked for ---------------
     # `value` is ALWAYS the eager operator under torch's DEFAULT autograd engine -- what a user of the drop-in API runs
@@ -453,6 +563,9 @@ def bench_chamfer(args, dist, world, rank, device):
     exchange_modes_ms, exchange_mode = None, (exchange.mode if exchange is not None else None)
     dt = run_timed(timed_fn, args.warmup, args.steps)
     ms = dt / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before anything else runs a step: `last` is the timed region's last step
+        dumped = dump_outputs(args.dump_outputs, dict(zip(CHAMFER_OUTPUTS, last)))
 
     modes = {want: ms}
     n_cal = 100
@@ -482,6 +595,15 @@ def bench_chamfer(args, dist, world, rank, device):
         torch.autograd.set_multithreading_enabled(False)
         modes["eager_calling_thread"] = run_timed(eager_step, args.warmup, args.steps) / args.steps * 1e3
         torch.autograd.set_multithreading_enabled(True)
+        if APART_CPUS:
+            # the headline's steps with the calling thread in another L3 domain (another NUMA node where there is
+            # one) than the engine's device thread: the hand-off a process the scheduler spreads that way pays
+            kept = os.sched_getaffinity(0)
+            os.sched_setaffinity(0, APART_CPUS)      # (0: the calling thread alone)
+            try:
+                modes["eager_threads_apart"] = run_timed(eager_step, args.warmup, args.steps) / args.steps * 1e3
+            finally:
+                os.sched_setaffinity(0, kept)
     compute_ms = exchange_ms = None
     if dist is not None:
         # the two legs by themselves: the same steps without the exchange, and the exchange with nothing beside it
@@ -619,6 +741,8 @@ def bench_chamfer(args, dist, world, rank, device):
     }
     if graph_note:
         out["config"]["launch_note"] = graph_note
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if want == "eager" and "ext" in modes and "eager_calling_thread" in modes:
         # The eager step under torch's default engine hands the backward to the engine's device thread and waits for it:
         # two thread wake-ups per step.  On a box with a slow host (observed on this pool: 0.107 ms against 0.078 for
@@ -757,7 +881,13 @@ def bench_chamfer(args, dist, world, rank, device):
             B, N, ("%.2f" % brute["fwd_ms"]) if brute else "1.8")
         out["other_distributions_fwd_ms"] = od
     if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU leg runs at N=1 only
-        out["cpu_baseline"] = cpu_baseline_chamfer(N, C)
+        # on every CPU the process may use, not on the one L3 domain the GPU timings keep to (pin_to_one_l3_domain)
+        kept = os.sched_getaffinity(0)
+        _set_affinity(ALL_CPUS or kept)
+        try:
+            out["cpu_baseline"] = cpu_baseline_chamfer(N, C)
+        finally:
+            _set_affinity(kept)
     # ---- which exchange?  Several ranks and no PP_SHARD_EXCHANGE: everything above ran on the native form (c10d's
     # all-gather).  Now the grouped send / receive form (p2p: every part over its own xGMI link) is tried -- 20 steps of
     # the timed function on each form -- and if it is faster the headline is measured again on it.  The p2p form has never
@@ -798,6 +928,8 @@ def bench_chamfer(args, dist, world, rank, device):
                     exchange = trial
                     dt2 = run_timed(timed_fn, args.warmup, args.steps)
                     ms2 = dt2 / args.steps * 1e3
+                    if args.dump_outputs and rank == 0:     # the headline's timed region is now this one
+                        out["dump_outputs"] = dump_outputs(args.dump_outputs, dict(zip(CHAMFER_OUTPUTS, last)))
                     out["ms_per_step_native_exchange"] = out["ms_per_step"]
                     out["ms_per_step"] = ms2
                     out["value"] = pairs_per_step / (ms2 * 1e-3)
@@ -834,12 +966,17 @@ def bench_fps(args, dist, world, rank, device):
     N = args.points or 65536
     npoint = 4096
     x = torch.from_numpy(S.unit_sphere(0, B, N)).to(device)
+    last = []    # the latest step's outputs (--dump-outputs), let go at the start of the next: its buffers are reused
 
     def step():
-        furthest_point_sample(x, npoint, NCHW=False, seedIdx=0)
+        del last[:]
+        last[:] = furthest_point_sample(x, npoint, NCHW=False, seedIdx=0)
 
     dt = timed_region(dist, step, args.steps, args.warmup, device)
     ms = dt / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, dict(zip(("idx", "points"), last)))
     updates = float(B) * (npoint - 1) * N * world
     alg_bytes = 12.0 * B * N + 4.0 * B * npoint
     gbs = alg_bytes / (ms * 1e-3) / 1e9
@@ -888,7 +1025,7 @@ def bench_fps(args, dist, world, rank, device):
                          "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "traffic": None,
                          "note": "serial chain of npoint-1 dependent steps: latency-bound, not HBM-bound"},
             "us_per_pick": ms * 1e3 / (npoint - 1),
-            "other_clouds_ms": other}
+            "other_clouds_ms": other, **({"dump_outputs": dumped} if dumped is not None else {})}
 
 
 # ------------------------------------------------------------- ball_query + group_points (config 4)
@@ -906,22 +1043,27 @@ def bench_ball_group(args, dist, world, rank, device):
 
     from pytorch_points_amd._ext import sampling as _sampling
     grad_out = None
+    last = {}    # the latest step's outputs (--dump-outputs), let go at the start of the next: its buffers are reused
 
     def step():
         nonlocal grad_out
+        last.clear()
         e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         e[0].record()
         idx = ball_query(r, ns, x, centres)
         e[1].record()
         out = grouping_operation(feats, idx)
         e[2].record()
+        last["idx"], last["grouped"] = idx, out
         if args.with_backward:
-            _sampling.group_points_grad(out, idx, N)     # dL/dout := out (any dense gradient)
+            last["grad_features"] = _sampling.group_points_grad(out, idx, N)     # dL/dout := out (any dense gradient)
         e[3].record()
         ev.append(e)
 
     dt = timed_region(dist, step, args.steps, args.warmup, device)
     torch.cuda.synchronize()
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
+    last.clear()
     bq_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev[-args.steps:]]))
     gp_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev[-args.steps:]]))
     gpg_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev[-args.steps:]])) if args.with_backward else None
@@ -999,7 +1141,8 @@ def bench_ball_group(args, dist, world, rank, device):
                          "frac_all_bytes_of_measured": gbs / peak_measured if peak_measured else None,
                          # PMC passes (profiles/r1/pmc_summary.txt): WRITE_SIZE 4096 MB exact, FETCH_SIZE
                          # 144 MB x2 (16-B loads read 1/2 on gfx950) = 288 MB
-                         "traffic": 4583e6 if (B, N, C, ns) == (32, 16384, 128, 64) else None}}
+                         "traffic": 4583e6 if (B, N, C, ns) == (32, 16384, 128, 64) else None},
+            **({"dump_outputs": dumped} if dumped is not None else {})}
 
 
 def _short(line):
@@ -1061,6 +1204,7 @@ def main():
         raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
     dist, world, rank, local = init_dist(args)
     device = torch.device("cuda", local)
+    host_cpus = pin_to_one_l3_domain(device)     # before the autograd engine starts its device thread
     fn = {"chamfer": bench_chamfer, "fps": bench_fps, "ball_group": bench_ball_group}[args.workload]
     out = fn(args, dist, world, rank, device)
     if args.workload == "chamfer" and world == 1 and args.launch == "all" and not args.no_extras \
@@ -1070,11 +1214,11 @@ def main():
         import copy
         torch.cuda.empty_cache()
         a3 = copy.copy(args)
-        a3.steps, a3.warmup = 5, 2
+        a3.steps, a3.warmup, a3.dump_outputs = 5, 2, None
         out["fps"] = _short(bench_fps(a3, None, 1, 0, device))
         torch.cuda.empty_cache()
         a4 = copy.copy(args)
-        a4.steps, a4.warmup, a4.with_backward = 10, 3, True
+        a4.steps, a4.warmup, a4.with_backward, a4.dump_outputs = 10, 3, True, None
         out["ball_group"] = _short(bench_ball_group(a4, None, 1, 0, device))
         torch.cuda.empty_cache()
         out["other_ops_ms"] = bench_other_ops(device)
@@ -1089,6 +1233,7 @@ def main():
     except OSError:
         pass
     if rank == 0:
+        out["host_cpus"] = host_cpus
         print(json.dumps(out), flush=True)
 
 

@@ -1,5 +1,6 @@
 """bench.py keeps its contract with the driver: one JSON line on stdout with the agreed fields, for every
 workload (small sizes here; the numbers are not checked, the shape of the line is)."""
+import glob
 import json
 import os
 import subprocess
@@ -114,3 +115,67 @@ def test_distributed_line_times_the_exchange_forms(cuda):
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")][0])
     assert d["exchange_mode"] == "p2p" and d["exchange_modes_ms"] is None and "coalesced send / recv" in d["exchange_issue"]
+
+
+def _dumped(d, out_dir):
+    import numpy as np
+    files = {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(os.path.join(out_dir, "*.npy"))}
+    assert set(files) == set(d["dump_outputs"]) and sum(a.nbytes for a in files.values()) <= 64 * 10 ** 6
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    return files
+
+
+@pytest.mark.parametrize("launch, seeds", [("eager", (2, 3)), ("ext", (2, 3)), ("graph", (0, 1))])
+def test_dump_outputs_are_what_the_last_timed_step_computed(cuda, tmp_path, launch, seeds):
+    """--dump-outputs: the timed path's last step as its caller receives it (nndistance's outputs, the coordinate
+    gradients), equal to the CPU oracle on the inputs of that step -- with 1 + 3 steps the fourth, input set B (seeds
+    2 / 3) for the alternating forms, set A for the graph (static inputs).  A second run gets the same inputs: the same
+    distances and indices, bit for bit; the gradients are added with atomics in no fixed order (the default, unordered
+    backward: test_gpu_deterministic.py), so both runs are held to the oracle at that form's tolerance."""
+    import numpy as np
+    import oracle
+    from pytorch_points_amd import synthetic as S
+    b, n = 2, 1024
+    runs = []
+    for i in range(2 if launch == "eager" else 1):
+        out_dir = str(tmp_path / str(i))
+        d = _run("--batch", str(b), "--points", str(n), "--launch", launch, "--no-cpu-baseline", "--no-extras",
+                 "--dump-outputs", out_dir)
+        runs.append(_dumped(d, out_dir))
+    x1, x2 = S.unit_sphere(seeds[0], b, n), S.unit_sphere(seeds[1], b, n)
+    d1, i1, d2, i2 = oracle.chamfer_forward(x1, x2)
+    g1, g2 = oracle.chamfer_backward(x1, x2, np.full((b, n), 1.0 / (b * n), np.float32),
+                                     np.full((b, n), 1.0 / (b * n), np.float32), i1, i2)
+    for got in runs:
+        for k, e in (("dist1", d1), ("dist2", d2), ("idx1", i1), ("idx2", i2)):
+            assert got[k].shape == e.shape and np.array_equal(got[k], e), k
+        for k, e in (("grad_xyz1", g1), ("grad_xyz2", g2)):
+            assert got[k].shape == e.shape and np.allclose(got[k], e, rtol=1e-5, atol=1e-9), k
+
+
+def test_dump_outputs_of_fps_and_ball_group(cuda, tmp_path):
+    """the other two workloads: FPS's indices and points, ball_query's indices and the grouped features equal to the
+    oracle; at the default ball_group size (4 GiB of grouped features) a sample within the 64 MB"""
+    import numpy as np
+    import oracle
+    from pytorch_points_amd import synthetic as S
+    d = _run("--workload", "fps", "--batch", "2", "--points", "8192", "--dump-outputs", str(tmp_path / "fps"))
+    got = _dumped(d, str(tmp_path / "fps"))
+    x = S.unit_sphere(0, 2, 8192)
+    idx = oracle.furthest_sampling(x, 4096)[0]
+    assert np.array_equal(got["idx"], idx) and np.array_equal(got["points"], x[np.arange(2)[:, None], idx])
+    d = _run("--workload", "ball_group", "--with-backward", "--batch", "2", "--points", "2048",
+             "--dump-outputs", str(tmp_path / "bg"))
+    got = _dumped(d, str(tmp_path / "bg"))
+    x = S.unit_sphere(0, 2, 2048)
+    bq = oracle.ball_query(np.ascontiguousarray(x[:, ::4]), x, 0.1, 64)
+    grouped = oracle.group_points(S.normal(2, (2, 128, 2048)), bq)
+    assert np.array_equal(got["idx"], bq) and np.array_equal(got["grouped"], grouped)
+    # the backward the step times: group_points_grad with dL/dgrouped := grouped (atomics: the unordered tolerance)
+    assert got["grad_features"].shape == (2, 128, 2048)
+    assert np.allclose(got["grad_features"], oracle.group_points_grad(grouped, bq, 2048), rtol=1e-5, atol=1e-6)
+    d = _run("--workload", "ball_group", "--with-backward", "--dump-outputs", str(tmp_path / "bg_full"))
+    _dumped(d, str(tmp_path / "bg_full"))
+    info = d["dump_outputs"]
+    assert set(info) == {"idx", "grouped", "grad_features"} and info["grouped"]["shape"] == [32, 128, 4096, 64]
+    assert all(0 < v["written"] < np.prod(v["shape"]) for v in info.values())
