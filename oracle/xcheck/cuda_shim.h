@@ -54,6 +54,12 @@ using std::max;
 using std::min;
 static inline unsigned min(unsigned a, int b) { return b < 0 ? 0u : std::min(a, (unsigned)b); }  // CUDA has this overload
 static inline int min(int a, unsigned b) { return (int)std::min((unsigned)std::max(a, 0), b); }
+// CUDA's floating-point min / max are fminf / fmaxf (fmin / fmax): a NaN argument yields the other one.  std::min(NaN, x)
+// returns NaN, which would put NaN into the FPS kernel's temp where the reference keeps the old value.
+static inline float min(float a, float b) { return fminf(a, b); }
+static inline float max(float a, float b) { return fmaxf(a, b); }
+static inline double min(double a, double b) { return fmin(a, b); }
+static inline double max(double a, double b) { return fmax(a, b); }
 
 // kernel<<<grid, block>>>(...): `body` is a closure that calls the kernel function
 static inline void launch(dim3 grid, dim3 block, const std::function<void()>& body, bool needs_barrier) {

@@ -3,6 +3,7 @@
 they produce, so that tests/test_oracle.py can hold the CPU oracle (O1) against it.
 
     python oracle/xcheck/ref_xcheck.py          # build container only: needs /root/reference
+    python oracle/xcheck/ref_xcheck.py --range  # the same on tests/golden/range_*.npz -> ref_xcheck_range.npz
 
 What it does: reads the `__global__` kernels of the reference by line range from /root/reference AT RUN TIME
 (their text is never stored in this repository: the generated C++ file and the binary live under a temporary
@@ -172,7 +173,67 @@ def run_all(L, out, tag):
             out["%s/%s/interp_grad" % (tag, name)] = gp
 
 
+def run_range(L, out, tag):
+    """the range corpus (tests/golden/gen_range.py): Chamfer, labeled Chamfer, FPS, ball_query and three_nn at the
+    extremes of the fp32 range, and three_nn / FPS with few finite knowns or non-finite points"""
+    f32, i32 = np.float32, np.int32
+
+    def chamfer(key, x1, x2, l1=None, l2=None):
+        b, n, c = x1.shape
+        m = x2.shape[1]
+        d1, d2 = np.zeros((b, n), f32), np.zeros((b, m), f32)
+        i1, i2 = np.zeros((b, n), i32), np.zeros((b, m), i32)
+        if l1 is None:
+            L.x_chamfer_forward(P(x1), P(x2), b, n, m, c, P(d1), P(i1), P(d2), P(i2))
+        else:
+            L.x_labeled_chamfer_forward(P(x1), P(x2), P(l1), P(l2), b, n, m, c, P(d1), P(i1), P(d2), P(i2))
+        for k, v in (("dist1", d1), ("idx1", i1), ("dist2", d2), ("idx2", i2)):
+            out["%s/%s/%s" % (tag, key, k)] = v
+
+    def fps(key, x, mm):
+        b, n, _ = x.shape
+        temp = np.full((b, n), 1e10, f32)
+        idx = np.zeros((b, mm), i32)
+        L.x_furthest_sampling(P(x), P(temp), P(idx), b, n, mm, 0)
+        out["%s/%s/idx" % (tag, key)] = idx
+        if "_jitter" not in key:   # (temp is compared on the lattice-exact families only: the fixture stays small)
+            out["%s/%s/temp" % (tag, key)] = temp
+
+    def three_nn(key, u, k):
+        b, n, _ = u.shape
+        d2, ti = np.zeros((b, n, 3), f32), np.zeros((b, n, 3), i32)
+        L.x_three_nn(P(u), P(k), P(d2), P(ti), b, n, k.shape[1])
+        out["%s/%s/dist2" % (tag, key)] = d2
+        out["%s/%s/idx" % (tag, key)] = ti
+
+    for path in sorted(glob.glob(os.path.join(GOLDEN, "range_*.npz"))):
+        name = os.path.basename(path)[:-4]
+        g = {k: np.ascontiguousarray(v) for k, v in np.load(path).items()}
+        if name == "range_special":
+            for f in (1, 2):
+                three_nn("%s/tn%d" % (name, f), g["tn_unknown%d" % f], g["tn_known%d" % f])
+            fps("%s/fps" % name, g["fps_xyz"], int(g["fps_npoint"]))
+            print(tag, name, "ok", flush=True)
+            continue
+        x1, x2 = g["xyz1"], g["xyz2"]
+        chamfer(name + "/chamfer", x1, x2)
+        if "label1" in g:
+            chamfer(name + "/labeled", x1, x2, np.ascontiguousarray(g["label1"].astype(f32)),
+                    np.ascontiguousarray(g["label2"].astype(f32)))
+        fps(name + "/fps", g["fps_xyz"], int(g["fps_npoint"]))
+        ctr = g["new_xyz"]
+        b, mm, _ = ctr.shape
+        ns = int(g["nsample"])
+        for j, r in enumerate(g["radii"]):
+            idx = np.zeros((b, mm, ns), i32)
+            L.x_ball_query(P(ctr), P(x2), P(idx), b, x2.shape[1], mm, ctypes.c_float(r), ns)
+            out["%s/%s/ball_r%d" % (tag, name, j)] = idx
+        three_nn(name + "/three_nn", ctr, x2)
+        print(tag, name, "ok", flush=True)
+
+
 def main():
+    corpus = "--range" in sys.argv[1:]
     if not os.path.isdir(REF):
         raise SystemExit("ref_xcheck.py: %s is not here (build container only); tests/golden/ref_xcheck.npz is the "
                          "committed result" % REF)
@@ -181,9 +242,10 @@ def main():
         src = generate(tmp)
         out = {}
         for tag, flags in (("nocontract", ["-ffp-contract=off"]), ("fma", ["-ffp-contract=fast", "-mfma"])):
-            run_all(build(tmp, src, tag, flags), out, tag)
-        np.savez_compressed(os.path.join(GOLDEN, "ref_xcheck.npz"), **out)
-        print("wrote tests/golden/ref_xcheck.npz:", len(out), "arrays")
+            (run_range if corpus else run_all)(build(tmp, src, tag, flags), out, tag)
+        name = "ref_xcheck_range.npz" if corpus else "ref_xcheck.npz"
+        np.savez_compressed(os.path.join(GOLDEN, name), **out)
+        print("wrote tests/golden/%s:" % name, len(out), "arrays")
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 

@@ -725,10 +725,13 @@ __global__ __launch_bounds__(kBkThreads) void fps_bucket_kernel(
           const float mx = rl(orec.x, ms), my = rl(orec.y, ms), mz = rl(orec.z, ms);
           const unsigned msec = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(orec.w), ms);
           // a lower eligible candidate fails against this one if this pick lowers its key, or if something this
-          // pick leaves behind in its own bucket could still be above it
+          // pick leaves behind in its own bucket could still be above it.  A pick with a NaN or inf coordinate
+          // (dist3(m, m) != 0) keeps its own temp and is the next pick again, so it is a round of its own; and a
+          // NaN distance fails too (!(dd >= temp), not dd < temp).
           const bool lower = o_el && okey < mkey;
           const float dd = dist3(orec.x, orec.y, orec.z, mx, my, mz);
-          if (lower && (last || dd < __uint_as_float(ohi) || !(ohi > msec)))
+          const bool mbad = dist3(mx, my, mz, mx, my, mz) != 0.0f;
+          if (lower && (last || mbad || !(dd >= __uint_as_float(ohi)) || !(ohi > msec)))
             __hip_atomic_fetch_max(&s_fail[buf], okey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           if (room < 4 * kBkWaves && !last) {  // (uniform; only the call's last rounds can run out of room)
             const int rank = __builtin_popcountll(__ballot(o_el && okey > mkey));

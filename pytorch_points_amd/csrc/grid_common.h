@@ -11,6 +11,11 @@
 namespace pp {
 
 constexpr int kGridMax = 32;                                  // cells per axis
+// A set (or a crowded cell's points) of extent below this is one cell of side 1, as identical points are.  The searches'
+// bounds are relative (kBoundSlack, 1e-4 h of slack on every face), but a squared distance below 2^-149 rounds to 0:
+// points up to ~2^-74 apart tie at 0 whatever cell they are in.  From cells of 2^-49 on (an extent of 2^-44 over 32
+// cells, a crowded cell's over at most 25 sub-cells) the relative slack covers that absolute error with room to spare.
+constexpr float kGridMinExtent = 0x1p-44f;
 constexpr int kGridCells = kGridMax * kGridMax * kGridMax;    // LDS counters: 128 KiB
 constexpr int kBuildThreads = 1024;
 
@@ -164,7 +169,7 @@ __device__ __attribute__((noinline)) void grid_refine_cells(f4* __restrict__ sor
         int g2 = (int)cbrtf((float)n);  // ~ one point per sub-cell if the points filled their box (they never do)
         g2 = g2 < 2 ? 2 : (g2 > kSubMaxAxis - 1 ? kSubMaxAxis - 1 : g2);
         sg.h = semax / (float)g2;
-        if (!(sg.h > 0.0f) || !__builtin_isfinite(sg.h)) sg.h = 1.0f;  // identical points: one sub-cell
+        if (!(sg.h > 0.0f) || !__builtin_isfinite(sg.h) || semax < kGridMinExtent) sg.h = 1.0f;  // (nearly) identical points: one sub-cell
         sg.invh = 1.0f / sg.h;
         auto cells2 = [&](float e) {
           const int c = (int)(e * sg.invh) + 1;
@@ -714,12 +719,13 @@ __device__ __forceinline__ void grid_build_set_impl(const float* __restrict__ re
   // first guess: ~2 points per cell if the cloud filled its box; cubic cells of side h
   int g0 = (int)ceilf(cbrtf(2.0f * (float)nr));
   g0 = g0 < 1 ? 1 : (g0 > kGridMax ? kGridMax : g0);
-  const bool degenerate = !forced && (any_bad || !(emax > 0.0f) || !__builtin_isfinite(emax));
+  const bool tiny = !forced && emax < kGridMinExtent;  // (also every squared distance in the set underflows)
+  const bool degenerate = !forced && (any_bad || !(emax > 0.0f) || !__builtin_isfinite(emax) || tiny);
   float h, invh;
   int gx, gy, gz;
   auto set_resolution = [&](int g) {
     h = emax / (float)g;
-    if (!(h > 0.0f) || !__builtin_isfinite(h)) h = 1.0f;
+    if (!(h > 0.0f) || !__builtin_isfinite(h) || tiny) h = 1.0f;
     invh = 1.0f / h;
     auto cells = [&](float e) {
       int c = (int)(e * invh) + 1;  // c*h > e: the box maximum lies inside the last cell
@@ -1252,7 +1258,7 @@ __device__ __forceinline__ int grid_build_set_fast(const float* __restrict__ ref
   PP_PHASE(3);
   const float ex = mxx - mnx, ey = mxy - mny, ez = mxz - mnz;
   const float emax = fmaxf(ex, fmaxf(ey, ez));
-  if (any_bad || !(emax > 0.0f) || !__builtin_isfinite(emax)) return 1;  // degenerate: the general path marks it (uniform)
+  if (any_bad || !(emax > 0.0f) || !__builtin_isfinite(emax) || emax < kGridMinExtent) return 1;  // degenerate: the general path marks it (uniform)
   int g0 = 1;  // the general path's first guess, ceil(cbrt(2 nr)) clamped to [1, 32], on the scalar unit (cbrtf: ~200 dependent
   while (g0 < kGridMax && g0 * g0 * g0 < 2 * nr) ++g0;  // vector instructions in every lane of a phase that is one latency chain)
   float h, invh;

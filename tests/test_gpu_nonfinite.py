@@ -130,3 +130,45 @@ def test_nonfinite_points_keep_the_grid_larger_sets(cuda, nref, nq):
     finally:
         k(0)
     assert _eq(out[0][0], out[1][0]) and _eq(out[0][1], out[1][1]), "%d refs: three_nn differs" % nref
+
+
+# FPS with a NaN or +-inf coordinate: such a point's own distance to itself is NaN, so its temp never falls (fminf
+# keeps the old value) and the reference picks it on every step after it first wins.  Unlike the operators above this is
+# compared with the oracle, not path against path: every FPS form and both chains of the bucketed kernel must emit the
+# reference's picks and temp.  N = 40000 takes the batched chain by default.
+_FPS_PATHS = [(1, 0, 0), (2, 0, 0), (3, 1, 0), (3, 1, 1), (3, 2, 0), (3, 2, 1)]   # (form, chain, sort)
+_FPS_POISON = {"one_nan": [(1000, 1, np.nan)], "one_inf": [(1000, 0, np.inf)], "one_neg_inf": [(1000, 2, -np.inf)],
+               "several": [(3, 0, np.nan), (777, 2, np.inf), (1000, 1, -np.inf), (2500, 0, np.nan), (4000, 1, np.inf)]}
+
+
+def _set_fps(form, chain, sort):
+    _knob("pp_debug_set_fps_v1")(form)
+    _knob("pp_debug_set_fps_bucket_chain")(chain)
+    _knob("pp_debug_set_fps_bucket_sort")(sort)
+
+
+@pytest.mark.parametrize("n", [4096, 40000])
+@pytest.mark.parametrize("case", sorted(_FPS_POISON))
+def test_nonfinite_fps_matches_oracle(cuda, case, n):
+    import oracle
+    from pytorch_points_amd._ext import sampling
+    x = S.unit_sphere(320, 2, n)
+    for k, c, val in _FPS_POISON[case]:   # batch element 1 stays clean
+        x[0, k, c] = val
+    m = 300
+    e_idx, e_temp = oracle.furthest_sampling(x, m, 0)
+    xt = torch.from_numpy(x).to(cuda)
+    for path in _FPS_PATHS:
+        _set_fps(*path)
+        try:
+            idx = torch.empty(2, m, dtype=torch.int32, device=cuda)
+            temp = torch.full((2, n), 1e10, dtype=torch.float32, device=cuda)
+            sampling.furthest_sampling(m, 0, xt, temp, idx)
+            torch.cuda.synchronize()
+        finally:
+            _set_fps(0, 0, 0)
+        assert sampling.furthest_sampling_status(cuda) == 0, path
+        got = idx.cpu().numpy()
+        assert np.array_equal(got, e_idx), "%s %s: first difference at pick %d: %s against %s" % (
+            case, path, int(np.argmax((got != e_idx).any(0))), got[0, :6].tolist(), e_idx[0, :6].tolist())
+        assert _eq(temp, torch.from_numpy(e_temp).to(cuda)), "%s %s: temp" % (case, path)
