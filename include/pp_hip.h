@@ -3,8 +3,8 @@
  * `_ext` hot path.
  *
  * Each entry point replaces one function of the reference's pybind modules
- * `pytorch_points._ext.losses` (_ext/nmdistance.cpp:30-34) and `pytorch_points._ext.sampling`
- * (_ext/sampling.cpp:205-216); the reference interface each one stands in for is cited beside it
+ * `pytorch_points._ext.losses` (_ext/nmdistance.cpp:30-34), `pytorch_points._ext.sampling`
+ * (_ext/sampling.cpp:205-216) and `pytorch_points._ext.linalg` (_ext/torch_batch_svd.cpp:240-245); the reference interface each one stands in for is cited beside it
  * (paths relative to /root/reference/pytorch_points/).
  *
  * Conventions
@@ -282,6 +282,18 @@ int pp_gather_backward_ordered_f32(const float* grad_out, const int* idx, float*
 int pp_three_interpolate_grad_ordered_f32(const float* grad_out, const int* idx, const float* weight,
                                           float* grad_points, int B, int C, int N, int M, void* workspace,
                                           size_t workspace_bytes, void* stream);
+
+/* ---- _ext.linalg ------------------------------------------------------------------------
+ * Replaces linalg.batch_svd_forward(a, is_sort, tol, max_sweeps) (torch_batch_svd.cpp:38-140, cuSOLVER gesvdj).
+ * a (batch,m,n), m,n in 1..32 -> a = U[:, :, :k] diag(s) V[:, :, :k]^T, k = min(m,n); s (batch,k) >= 0;
+ * full != 0: U (batch,m,m), V (batch,n,n); full == 0: U (batch,m,k), V (batch,n,k).  One-sided Jacobi: a column pair is
+ * converged when |w_p.w_q| <= tol ||w_p|| ||w_q||; at most max_sweeps sweeps.  sort != 0: s descending (ties to the
+ * lower column).  info (batch) int32, nullable: sweeps used (1..max_sweeps), -1 not converged, -2 a non-finite entry
+ * (then that matrix's s, U and V are NaN).  Columns of U (V) beyond k or with s == 0 are a deterministic orthonormal
+ * completion.  Each matrix's result depends on that matrix alone.  PP_EINVAL: m or n outside 1..32, batch < 0,
+ * max_sweeps < 1, tol < 0 or NaN, a null pointer with batch > 0. */
+int pp_batch_svd_f32(const float* a, float* u, float* s, float* v, int* info, long long batch, int m, int n,
+                     int full, int sort, float tol, int max_sweeps, void* stream);
 
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */

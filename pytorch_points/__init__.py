@@ -2,10 +2,10 @@
 ``pytorch_points_amd``, so code written against the reference's hot-path API --
 
     from pytorch_points.network.model_loss import nndistance
-    from pytorch_points.network.operations import QueryAndGroup, gather_points, ball_query
-    from pytorch_points.network.geo_operations import furthest_point_sample
+    from pytorch_points.network.operations import QueryAndGroup, gather_points, ball_query, batch_svd
+    from pytorch_points.network.geo_operations import furthest_point_sample, batch_normals
     from pytorch_points.network.pointnet2_utils import three_nn, three_interpolate
-    from pytorch_points._ext import losses, sampling
+    from pytorch_points._ext import losses, sampling, linalg
 
 -- runs unchanged with this repository on ``sys.path`` (no install call).  This module replaces
 itself in ``sys.modules`` with ``pytorch_points_amd`` and registers the sub-modules of the path;

@@ -2,10 +2,10 @@
 
 Drop-in for the reference's operator API on that path only:
     pytorch_points.network.model_loss.{nndistance, labeled_nndistance}
-    pytorch_points.network.operations.{gather_points, ball_query, grouping_operation, QueryAndGroup}
-    pytorch_points.network.geo_operations.furthest_point_sample
+    pytorch_points.network.operations.{gather_points, ball_query, grouping_operation, QueryAndGroup, batch_svd}
+    pytorch_points.network.geo_operations.{furthest_point_sample, batch_normals}
     pytorch_points.network.pointnet2_utils.{three_nn, three_interpolate, QueryAndGroup, GroupAll}
-    pytorch_points._ext.{losses, sampling}
+    pytorch_points._ext.{losses, sampling, linalg}
 Host code is Python on PyTorch-ROCm (device memory, streams, torch.distributed); the kernels are
 hand-written HIP in csrc/, reached through the C ABI of libpp_hip.so (include/pp_hip.h).
 """
@@ -22,7 +22,7 @@ def install_as_pytorch_points():
     ``from pytorch_points.network.model_loss import nndistance`` resolves here."""
     import importlib
     import sys
-    names = ["", "._ext", "._ext.losses", "._ext.sampling", ".network", ".network.model_loss",
+    names = ["", "._ext", "._ext.losses", "._ext.sampling", "._ext.linalg", ".network", ".network.model_loss",
              ".network.operations", ".network.geo_operations", ".network.pointnet2_utils"]
     for suffix in names:
         mod = importlib.import_module(__name__ + suffix)

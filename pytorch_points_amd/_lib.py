@@ -65,6 +65,7 @@ SIGNATURES = {
     "pp_three_nn_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
     "pp_three_interpolate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "pp_three_interpolate_grad_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_batch_svd_f32": [_P, _P, _P, _P, _P, ctypes.c_longlong, _I, _I, _I, _I, _F, _I, _P],
 }
 _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_bytes": _c_size_t,
              "pp_nmdistance_forward_workspace_bytes": _c_size_t,

@@ -1,10 +1,11 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
-furthest_point_sample (reference network/geo_operations.py:11-64).  The mesh-geometry functions of that
-file are out of scope."""
+furthest_point_sample (reference network/geo_operations.py:11-64) and the PCA point normals batch_normals
+(:88-126).  The mesh-geometry functions of that file are out of scope."""
 import torch
 
+from .. import ops
 from .._ext import sampling
-from .operations import gather_points
+from .operations import batch_svd, gather_points
 
 _FAR = 1e10   # initial running minimum of every point (reference :29)
 
@@ -72,3 +73,29 @@ def furthest_point_sample(xyz, npoint, NCHW=True, seedIdx=0):
         idx = _furthest_point_sample(points_last, npoint, seedIdx)
         chosen = gather_points(points_last.transpose(2, 1).contiguous(), idx)   # (B, 3, npoint)
     return idx, (chosen if NCHW else chosen.transpose(2, 1).contiguous())
+
+
+def batch_normals(points, base=None, nn_size=20, NCHW=True, idx=None):
+    """Normals of ``points`` (B,C,M) -- (B,M,C) when not ``NCHW`` -- by PCA of their ``nn_size`` nearest neighbours in
+    ``base`` (default: ``points``): the right singular vector of the smallest singular value of each centred
+    neighbourhood.  ``idx`` (B,M,nn_size): neighbours given instead of searched.  Returns ``(normals, idx)``, normals in
+    the layout of ``points``; the sign of a normal is not defined (reference geo_operations.py:88-126, with
+    pytorch_points_amd.ops.knn_points in place of pytorch3d).  Differentiable through batch_svd."""
+    if base is None:
+        base = points
+    if NCHW:
+        points = points.transpose(2, 1).contiguous()
+        base = base.transpose(2, 1).contiguous()
+    assert(nn_size < base.shape[1])
+    batch_size, M, C = points.shape
+    if idx is None:
+        _, idx, grouped_points = ops.knn_points(points, base, K=nn_size, return_nn=True)
+    else:
+        grouped_points = torch.gather(base.unsqueeze(1).expand(-1, M, -1, -1), 2, idx.unsqueeze(-1).expand(-1, -1, -1, C))
+    group_center = torch.mean(grouped_points, dim=2, keepdim=True)
+    centred = grouped_points - group_center
+    _, _, V = batch_svd(centred.reshape(-1, nn_size, C))
+    normals = V[:, :, -1].reshape(batch_size, M, C)
+    if NCHW:
+        normals = normals.transpose(1, 2)
+    return normals, idx

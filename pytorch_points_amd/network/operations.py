@@ -1,9 +1,9 @@
 """``pytorch_points.network.operations`` -- the part on the hot path: gather_points, ball_query,
-grouping_operation, QueryAndGroup (reference: network/operations.py:38-213).  channel_shuffle,
-jitter, batch_svd and the torch one-liners of that file are out of scope."""
+grouping_operation, QueryAndGroup (reference: network/operations.py:38-213), and batch_svd (:215-258).
+channel_shuffle, jitter and the torch one-liners of that file are out of scope."""
 import torch
 
-from .._ext import sampling
+from .._ext import linalg, sampling
 
 
 class GatherFunction(torch.autograd.Function):
@@ -140,3 +140,33 @@ class QueryAndGroup(torch.nn.Module):
         if features is not None:
             parts.append(grouping_operation(features, members))
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+class BatchSVDFunction(torch.autograd.Function):
+    """Batched SVD of (B, M, N) fp32 matrices, M, N <= 32 (reference operations.py:215-245): ``x = U diag(S) V^T`` with
+    the thin U (B,M,k), S (B,k) descending, V (B,N,k), k = min(M, N).  A CPU input runs on the GPU and its outputs
+    and gradient come back to the CPU, as in the reference.  The kernel writes the thin factors directly
+    (pp_batch_svd_f32 with full = 0) where the reference computes full ones and narrows them."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.device = x.device
+        x = x.cuda()
+        U, S, V = linalg.batch_svd_forward(x, True, 1e-7, 100, full=False)
+        ctx.save_for_backward(x, U, S, V)
+        return U.to(ctx.device), S.to(ctx.device), V.to(ctx.device)
+
+    @staticmethod
+    def backward(ctx, grad_u, grad_s, grad_v):
+        x, U, S, V = ctx.saved_tensors
+        dev = x.device
+        grads = [g.to(dev) if g is not None else None for g in (grad_u, grad_s, grad_v)]
+        grad_out = linalg.batch_svd_backward(grads, x, True, True, U, S, V)
+        return grad_out.to(device=ctx.device)
+
+
+def batch_svd(x):
+    """``U, S, V = batch_svd(x)`` for x (B, M, N), so that x = U diag(S) V^T: U (B,M,k), S (B,k) descending,
+    V (B,N,k), k = min(M, N) (reference operations.py:248-258)."""
+    assert(x.dim() == 3)
+    return BatchSVDFunction.apply(x)
