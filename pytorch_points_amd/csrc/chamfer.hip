@@ -1122,8 +1122,7 @@ extern "C" int pp_nmdistance_backward_f32(const float* xyz1, const float* xyz2,
     float* g = N == 0 ? gradxyz2 : gradxyz1;
     const long long n = (N == 0 ? t2 : t1) * C;
     if (!g) return PP_EINVAL;
-    hipError_t e = hipMemsetAsync(g, 0, (size_t)n * sizeof(float), s);
-    return (int)e;
+    return (int)pp::fill_bytes(g, 0, (size_t)n * sizeof(float), s);
   }
   if (!xyz1 || !xyz2 || !graddist1 || !graddist2 || !idx1 || !idx2 || !gradxyz1 || !gradxyz2)
     return PP_EINVAL;

@@ -189,7 +189,7 @@ static int typed_backward(const T* xyz1, const T* xyz2, const T* graddist1, cons
   if (N == 0 || M == 0) {  // no pairs: gradients are zero
     T* g = N == 0 ? gradxyz2 : gradxyz1;
     if (!g) return PP_EINVAL;
-    return (int)hipMemsetAsync(g, 0, (size_t)((N == 0 ? t2 : t1) * C) * sizeof(T), s);
+    return (int)pp::fill_bytes(g, 0, (size_t)((N == 0 ? t2 : t1) * C) * sizeof(T), s);
   }
   if (!xyz1 || !xyz2 || !graddist1 || !graddist2 || !idx1 || !idx2 || !gradxyz1 || !gradxyz2) return PP_EINVAL;
   const long long blocks = (t1 + t2 + 255) / 256;

@@ -3141,15 +3141,31 @@ struct RouteWord {
   unsigned* dev;
 };
 static std::atomic<RouteWord*> g_route_word[64];  // per device; allocated once, never freed
-static const RouteWord* route_word(int dev) {
+// nullptr = this call does not route (the list kernel serves every direction: slower, the same bits).  The word is never
+// allocated while `s` is being captured into a graph: measured on gfx950, a hipHostMalloc during a global-mode capture
+// invalidates it (the cold-capture test then fails with hipErrorStreamCaptureInvalidated, 901), as CUDA's rule has it.
+// So a capture that comes first in a process does not route,
+// and one that comes later routes with the word an eager call allocated.  A failure tolerated here is taken off the
+// thread's last-error slot, or the next launch check would report it as a failed launch.
+static const RouteWord* route_word(int dev, hipStream_t s) {
   if (dev < 0 || dev >= 64) return nullptr;
   RouteWord* w = g_route_word[dev].load(std::memory_order_acquire);
   if (w) return w;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  if (st != hipStreamCaptureStatusNone) return nullptr;
   unsigned* host = nullptr;
   unsigned* devp = nullptr;
-  if (hipHostMalloc((void**)&host, 64, hipHostMallocMapped) != hipSuccess || !host) return nullptr;
+  if (hipHostMalloc((void**)&host, 64, hipHostMallocMapped) != hipSuccess || !host) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
   *host = 0u;
   if (hipHostGetDevicePointer((void**)&devp, host, 0) != hipSuccess || !devp) {
+    (void)hipGetLastError();
     (void)hipHostFree(host);
     return nullptr;
   }
@@ -3227,7 +3243,11 @@ static int grid_forward(const float* xyz1, const float* xyz2, const float* label
   bool routing = false;
   if (two_stage && g_route_mode != 1) {
     int dev = 0;
-    const RouteWord* rw = hipGetDevice(&dev) == hipSuccess ? route_word(dev) : nullptr;
+    const RouteWord* rw = nullptr;
+    if (hipGetDevice(&dev) == hipSuccess)
+      rw = route_word(dev, s);
+    else
+      (void)hipGetLastError();  // (tolerated: no routing)
     if (rw) {
       route_dev = rw->dev;
       epoch = g_route_epoch.fetch_add(1u, std::memory_order_relaxed) + 1u;
@@ -3278,8 +3298,10 @@ static int grid_forward(const float* xyz1, const float* xyz2, const float* label
     if (ncu == 0) {
       int dev = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          ncu <= 0)
+          ncu <= 0) {
+        (void)hipGetLastError();  // (tolerated: the chip's count)
         ncu = 256;
+      }
       cus.store(ncu, std::memory_order_relaxed);
     }
 #define PP_LAUNCH_A(TQ_, CAP_, PER_CU_, WPE_)                                                                          \

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_block_kernel(const float* __r
 // The granule IS the flag (no separate flag, no fence: nothing else is handed over).  Two ring
 // slots suffice: a workgroup can publish step j+2 only after it has read every member's step j+1
 // granule, which that member publishes only after it has read all of step j.  The ring is reset
-// by a hipMemsetAsync node in front of every launch (tag 0xFF never matches: tags are 7 bits).
+// by a fill launch in front of every launch (pp::fill_bytes; tag 0xFF never matches: tags are 7 bits).
 // (Tried and rejected: publishing the winner's coordinates with the key -- four granules per member
 // and 64 polling lanes -- to drop the dependent scalar load of x_old: 1.78 -> 2.50 us per pick.)
 // Correctness does not depend on placement or dispatch order; it needs the B*CL workgroups to be
@@ -291,12 +291,16 @@ void launch_fps_cluster(const float* xyz, float* temp, int* idx, int B, int N, i
 // so the launch must never exceed this; kMaxClusterBlocks (the whole chip) only sizes the workspace, which
 // must not depend on a device being present.
 constexpr int kMaxClusterBlocks = 256;
+// A failed query means "no cluster" (0); its error is taken off the thread's last-error slot, or the launch check
+// behind the kernel chosen instead would report it as a failed launch.
 template <int R>
 int resident_cluster_blocks() {
   int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fps_cluster_kernel<R>, kClThreads, 0) != hipSuccess) return 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fps_cluster_kernel<R>, kClThreads, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
   if (per_cu < 1) return 0;
   return cus < kMaxClusterBlocks ? cus : kMaxClusterBlocks;  // one per CU, whatever the query allows beyond that
 }
@@ -425,7 +429,7 @@ extern "C" int pp_furthest_sampling_gather_f32(const float* xyz, float* temp, in
     // reset the ring (tag 0xFF never matches a step tag).  The status word in front of it is STICKY: the
     // caller zeroes it once after allocating the workspace, a timed-out wait sets it, and it stays set until
     // the caller clears it -- so a failure cannot be wiped out by the next call before anybody has looked.
-    hipError_t e = hipMemsetAsync((char*)workspace + kFpsErrBytes, 0xFF, ring_bytes(B, N), s);
+    hipError_t e = pp::fill_bytes((char*)workspace + kFpsErrBytes, 0xFF, ring_bytes(B, N), s);
     if (e != hipSuccess) return (int)e;
     u64* ring = (u64*)((char*)workspace + kFpsErrBytes);
     unsigned* err = (unsigned*)workspace;

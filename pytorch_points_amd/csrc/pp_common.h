@@ -40,17 +40,51 @@ struct DeviceFlags {
 };
 
 // Raise a kernel's dynamic-LDS limit (needed above 64 KiB).  Once per device per kernel: `flags`
-// is a zero-initialised static owned by the call site.
+// is a zero-initialised static owned by the call site.  A failure is returned, and taken off the thread's
+// last-error slot: a caller that falls back to another kernel must not have it reported by that kernel's launch
+// check, nor the next call of any operator by its own.
 template <typename K>
 inline hipError_t allow_big_lds(K kernel, int bytes, DeviceFlags& flags) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return e;
+  }
   if (dev < 0 || dev >= 64) dev = 63;
   if (dev != 63 && flags.f[dev].load(std::memory_order_acquire)) return hipSuccess;
   e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) flags.f[dev].store(true, std::memory_order_release);
+  if (e == hipSuccess)
+    flags.f[dev].store(true, std::memory_order_release);
+  else
+    (void)hipGetLastError();
   return e;
+}
+
+// Byte fill on a stream, as kernels of the library's own (a zero output of an accumulating backward, a ring reset).
+// Not hipMemsetAsync: on the ROCm this was measured with, a 1 MiB hipMemsetAsync captured into a graph zeroed the whole
+// buffer on the first replay and left half of it untouched on later ones (a standalone graph holding nothing else;
+// 4 KiB, 4 MiB and 16 MiB were zeroed every time).  test_gpu_graphs.py's test_grouping_operation[global_atomics] met it
+// as stale values in a 1 MiB gradient.  A kernel node is ordered and complete like every other launch.  (Templates:
+// defined once per program although every source includes this header.)
+template <int>
+__global__ void fill_u32_kernel(unsigned* p, unsigned v, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = v;
+}
+template <int>
+__global__ void fill_u8_kernel(unsigned char* p, unsigned char v, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = v;
+}
+inline hipError_t fill_bytes(void* p, unsigned char byte, size_t bytes, hipStream_t s) {
+  if (bytes == 0) return hipSuccess;
+  const bool words = ((uintptr_t)p & 3u) == 0 && (bytes & 3u) == 0;
+  const long long n = words ? (long long)(bytes / 4) : (long long)bytes;
+  const long long blocks = (n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192;
+  if (words)
+    fill_u32_kernel<0><<<dim3((unsigned)blocks), dim3(256), 0, s>>>((unsigned*)p, 0x01010101u * byte, n);
+  else
+    fill_u8_kernel<0><<<dim3((unsigned)blocks), dim3(256), 0, s>>>((unsigned char*)p, byte, n);
+  return hipGetLastError();
 }
 
 __device__ __forceinline__ float chamfer_d3(float rx, float ry, float rz, float qx, float qy,

@@ -533,7 +533,7 @@ bool launch_group_dma1(const float* points, const int* idx, float* out, int B, i
   const size_t lds = (size_t)passes * kDma1Threads * 16;
   if (lds > 72 * 1024 || chunks > 0x7fffffLL || blocks > 0x7fffffffLL) return false;
   static pp::DeviceFlags lds_ok;
-  if (pp::allow_big_lds(group_points_dma1_kernel<V, NT>, 80 * 1024, lds_ok) != hipSuccess) return false;
+  if (pp::allow_big_lds(group_points_dma1_kernel<V, NT>, 80 * 1024, lds_ok) != hipSuccess) return false;  // (another kernel)
   group_points_dma1_kernel<V, NT><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
       points, idx, out, B, C, N, P, (int)chunks, passes, cgroups, c_per_group, obs);
   return true;
@@ -1330,6 +1330,10 @@ extern "C" int pp_group_points_grad_f32(const float* grad_out, const int* idx, f
 static int group_points_grad_launch(const float* grad_out, const int* idx, float* grad_points, int B, int C, int N,
                                     int npoint, int nsample, long long grad_out_batch_stride, void* stream,
                                     bool overwrite);
+static int zero_f32(float* p, size_t n, hipStream_t s) {  // (pp::fill_bytes: not hipMemsetAsync)
+  return (int)pp::fill_bytes(p, 0, n * sizeof(float), s);
+}
+
 extern "C" int pp_group_points_grad_strided_f32(const float* grad_out, const int* idx, float* grad_points,
                                                 int B, int C, int N, int npoint, int nsample,
                                                 long long grad_out_batch_stride, void* stream) {
@@ -1374,8 +1378,8 @@ static int group_points_grad_launch(const float* grad_out, const int* idx, float
       return PP_OK;
     }
     if (overwrite) {  // (the forms below accumulate)
-      const hipError_t e = hipMemsetAsync(grad_points, 0, (size_t)B * C * N * sizeof(float), (hipStream_t)stream);
-      if (e != hipSuccess) return (int)e;
+      const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
+      if (e != PP_OK) return e;
       overwrite = false;
     }
     if (vec && (size_t)N * sizeof(float) <= 160 * 1024) {  // fp32 column (kept for comparison: ds_add_f32 is slow)
@@ -1390,8 +1394,8 @@ static int group_points_grad_launch(const float* grad_out, const int* idx, float
     }
   }
   if (overwrite) {
-    const hipError_t e = hipMemsetAsync(grad_points, 0, (size_t)B * C * N * sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
+    const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
+    if (e != PP_OK) return e;
   }
   const long long cols = (P + 255) / 256;
   const int cpb = pick_c_per_block(cols, B, C);
@@ -1549,11 +1553,11 @@ extern "C" int pp_group_points_grad_out_ws_f32(const float* grad_out, const int*
   if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
   if (B == 0 || C == 0 || N == 0) return PP_OK;
   if (!grad_points) return PP_EINVAL;
-  if (P == 0) return (int)hipMemsetAsync(grad_points, 0, (size_t)B * C * N * sizeof(float), (hipStream_t)stream);
+  if (P == 0) return zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
   if (grad_out && idx && P <= 4LL * N && grad_out_batch_stride >= (long long)C * P &&
       scatter_ok(B, C, P, 1, N, 0, workspace, workspace_bytes)) {  // the sorted form accumulates
-    const hipError_t e = hipMemsetAsync(grad_points, 0, (size_t)B * C * N * sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
+    const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
+    if (e != PP_OK) return e;
     return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, grad_out_batch_stride, workspace,
                        (hipStream_t)stream, false);
   }

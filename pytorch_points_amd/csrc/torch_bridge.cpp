@@ -45,8 +45,11 @@ Tensor workspace(const c10::Device& dev, hipStream_t stream, size_t nbytes, bool
   if (nbytes == 0) return Tensor();
   const auto opts = torch::TensorOptions().dtype(torch::kUInt8).device(dev);
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+  if (hipStreamIsCapturing(stream, &st) != hipSuccess) {
+    (void)hipGetLastError();  // (not the kernels' launch check's to report)
     return torch::empty({(int64_t)nbytes}, opts);
+  }
+  if (st != hipStreamCaptureStatusNone) return torch::empty({(int64_t)nbytes}, opts);
   std::lock_guard<std::mutex> lock(g_ws_mutex);
   if (g_ws.size() > 16) g_ws.clear();
   Tensor& slot = g_ws[std::make_tuple((int)dev.index(), (void*)stream, labeled)];
