@@ -295,6 +295,31 @@ int pp_three_interpolate_grad_ordered_f32(const float* grad_out, const int* idx,
 int pp_batch_svd_f32(const float* a, float* u, float* s, float* v, int* info, long long batch, int m, int n,
                      int full, int sort, float tol, int max_sweeps, void* stream);
 
+/* ---- mean value coordinates ---------------------------------------------------------------
+ * Replaces network.geo_operations.mean_value_coordinates_3D(query, vertices, faces, verbose) (geo_operations.py:349-456,
+ * torch composition); contract in DESIGN.md "Mean value coordinates".  query (B,P,3), vertices (B,N,3), faces int64
+ * (B,F,3) read at faces + b * faces_batch_stride (elements; 0 = one face list for every batch element).
+ * Forward -> wj (B,P,N) normalised weights; sums (B,P) the divisor used; codes (B,P) int32 branch bits (1 zero row sum,
+ * 2 on a face, 4 on a vertex, 8 an out-of-range face index: the row is NaN); wi (B,P,F,3), nullable, the per-face
+ * weights after the face branches.  Backward: grad_wj (B,P,N), grad_wi (nullable) -> grad_query (B,P,3),
+ * grad_vertices (B,N,3), with a workspace of pp_mvc3d_workspace_bytes(B,P,N,sizeof element) bytes.  No floating-point
+ * atomics: every output is reproducible bit for bit, and a query's row does not depend on the other queries. */
+size_t pp_mvc3d_workspace_bytes(int B, int P, int N, int elem_bytes);
+int pp_mvc3d_forward_f32(const float* query, const float* vertices, const long long* faces,
+                         long long faces_batch_stride, float* wj, float* sums, int* codes, float* wi, int B, int P,
+                         int N, int F, void* stream);
+int pp_mvc3d_forward_f64(const double* query, const double* vertices, const long long* faces,
+                         long long faces_batch_stride, double* wj, double* sums, int* codes, double* wi, int B, int P,
+                         int N, int F, void* stream);
+int pp_mvc3d_backward_f32(const float* query, const float* vertices, const long long* faces,
+                          long long faces_batch_stride, const float* wj, const float* sums, const int* codes,
+                          const float* grad_wj, const float* grad_wi, float* grad_query, float* grad_vertices, int B,
+                          int P, int N, int F, void* workspace, size_t workspace_bytes, void* stream);
+int pp_mvc3d_backward_f64(const double* query, const double* vertices, const long long* faces,
+                          long long faces_batch_stride, const double* wj, const double* sums, const int* codes,
+                          const double* grad_wj, const double* grad_wi, double* grad_query, double* grad_vertices,
+                          int B, int P, int N, int F, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -1,8 +1,10 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
-furthest_point_sample (reference network/geo_operations.py:11-64) and the PCA point normals batch_normals
-(:88-126).  The mesh-geometry functions of that file are out of scope."""
+furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
+(:88-126) and the cage coordinates mean_value_coordinates_3D (:349-456).  The other mesh-geometry functions of that
+file are out of scope."""
 import torch
 
+from .. import mvc as _mvc
 from .. import ops
 from .._ext import sampling
 from .operations import batch_svd, gather_points
@@ -99,3 +101,11 @@ def batch_normals(points, base=None, nn_size=20, NCHW=True, idx=None):
     if NCHW:
         normals = normals.transpose(1, 2)
     return normals, idx
+
+
+def mean_value_coordinates_3D(query, vertices, faces, verbose=False):
+    """Mean value coordinates (Ju et al. 2005) of ``query`` (B,P,3) with respect to the closed triangle cage
+    ``vertices`` (B,N,3), ``faces`` (B,F,3): ``wj`` (B,P,N), and ``(wj, wi)`` with ``verbose``, ``wi`` (B,P,F,3) the
+    per-face weights.  CUDA fp32 / fp64 run fused HIP kernels; other devices and dtypes a torch composition of the
+    same contract (pytorch_points_amd.mvc, DESIGN.md "Mean value coordinates")."""
+    return _mvc.mean_value_coordinates_3D(query, vertices, faces, verbose)
