@@ -31,13 +31,14 @@ def tau(m, n):
     return 8 * max(m, n) * 2.0 ** -23
 
 
-def check_contract(a, u, s, v, full, vectors=True, scale=1.0):
-    """every check of the accuracy contract; ``scale`` multiplies the input and s before comparing (range tests)"""
+def check_contract(a, u, s, v, full, vectors=True, scale=1.0, ref=None):
+    """every check of the accuracy contract; ``scale`` multiplies the input and s before comparing (range tests);
+    ``ref`` is ``np.linalg.svd`` of that scaled fp64 input when the caller has it already"""
     b, m, n = a.shape
     k = min(m, n)
     t = tau(m, n)
     a64 = a.astype(np.float64) * scale
-    u64, s64, vt64 = np.linalg.svd(a64)
+    u64, s64, vt64 = np.linalg.svd(a64) if ref is None else ref
     s = s.astype(np.float64) * scale
     assert u.shape == (b, m, m if full else k) and v.shape == (b, n, n if full else k) and s.shape == (b, k)
     assert np.isfinite(u).all() and np.isfinite(v).all() and np.isfinite(s).all()
@@ -152,6 +153,95 @@ def test_normals_size_batch_in_full(cuda):
     assert ((info >= 1) & (info <= 100)).all()
 
 
+# ------------------------------------------------------------------------------------------- every layout, every mode
+# pp_batch_svd_f32 picks one of 38 instantiations by (R, K) = (max(m, n), min(m, n)): svd_lane_kernel<RM, K> for
+# K <= 4 (RM = R rounded up to a multiple of 4: 32 of them) and svd_cols_kernel<RM, G> above ((8,8), (16,8), (32,8),
+# (16,16), (32,16), (32,32)).  Every (m, n) runs; the batch of 67 leaves the last group of every column layout (8, 16
+# or 32 matrices a block) and the last wave of the lane layout partial.
+SWEEP_SCALES = (1.0, 1e-3, 1e3, 1e-30, 1e30)
+SWEEP_GAUSSIAN = 12 * len(SWEEP_SCALES)       # rows 0..59 Gaussian, 60 graded: the full contract
+SWEEP_STRUCTURED = 4                          # rank 1, rank k - 1, zero, c I: no singular-vector check (ties)
+SWEEP_BATCH = SWEEP_GAUSSIAN + 1 + SWEEP_STRUCTURED + 2   # then one NaN and one +inf matrix
+
+
+def sweep_batch(m, n, rng):
+    k = min(m, n)
+    parts = [gaussian(rng, 12, m, n) * np.float32(c) for c in SWEEP_SCALES]
+    parts.append(graded(rng, 1, m, n))
+    parts.append((rng.standard_normal((1, m, 1)) @ rng.standard_normal((1, 1, n))).astype(np.float32))
+    parts.append((rng.standard_normal((1, m, k - 1)) @ rng.standard_normal((1, k - 1, n))).astype(np.float32))
+    parts.append(np.zeros((1, m, n), np.float32))
+    parts.append((np.eye(m, n) * rng.uniform(0.5, 2.0))[None].astype(np.float32))
+    bad = gaussian(rng, 2, m, n)
+    bad[0, rng.integers(m), rng.integers(n)] = np.nan
+    bad[1, rng.integers(m), rng.integers(n)] = np.inf
+    parts.append(bad)
+    a = np.concatenate(parts)
+    assert a.shape[0] == SWEEP_BATCH
+    return a
+
+
+def bits(x):
+    return np.ascontiguousarray(x).view(np.int32)
+
+
+def permute_columns(x, perm):
+    """columns 0..k-1 of every matrix of x (b, r, c) reordered by perm (b, k); columns k.. stay in place"""
+    out = x.copy()
+    out[:, :, :perm.shape[1]] = np.take_along_axis(x[:, :, :perm.shape[1]], perm[:, None, :], axis=2)
+    return out
+
+
+@pytest.mark.parametrize("n", range(1, 33))
+@pytest.mark.parametrize("m", range(1, 33))
+def test_every_shape_sorted_unsorted_full_and_thin(cuda, m, n):
+    a = sweep_batch(m, n, np.random.default_rng(3000 + 40 * m + n))
+    k = min(m, n)
+    nv = SWEEP_GAUSSIAN + 1
+    fin = np.arange(SWEEP_BATCH) < nv + SWEEP_STRUCTURED
+    ref = np.linalg.svd(a[fin].astype(np.float64))
+    ref_v = tuple(x[:nv] for x in ref)
+    ref_s = tuple(x[nv:] for x in ref)
+
+    def contract(u, s, v, full):
+        check_contract(a[:nv], u[:nv], s[:nv], v[:nv], full, ref=ref_v)
+        check_contract(a[nv:fin.sum()], u[nv:fin.sum()], s[nv:fin.sum()], v[nv:fin.sum()], full, vectors=False,
+                       ref=ref_s)
+
+    res = {}
+    for full in (True, False):
+        for sort in (True, False):
+            res[full, sort] = svd(cuda, a, full, sort)
+        u, s, v, info = res[full, True]
+        contract(u, s, v, full)
+        assert (((info >= 1) & (info <= 100)) | (info == -1))[fin].all(), info
+        assert np.isnan(u[~fin]).all() and np.isnan(s[~fin]).all() and np.isnan(v[~fin]).all()
+        assert (info[~fin] == -2).all()
+
+        # unsorted: the same columns, placed by original column; the kernel ranks ties lower column first
+        uu, su, vu, iu = res[full, False]
+        perm = np.argsort(-su, axis=1, kind="stable")
+        assert np.array_equal(bits(np.take_along_axis(su, perm, axis=1)), bits(s))
+        assert np.array_equal(iu, info)
+        up, vp = permute_columns(uu, perm), permute_columns(vu, perm)
+        (ys, zs), (yp, zp) = ((u, v), (up, vp)) if m >= n else ((v, u), (vp, up))
+        assert np.array_equal(bits(zp), bits(zs))
+        # Y columns with sigma > 0 are w_j / sigma_j in either order; the others are completions built against the
+        # columns already in place, so they differ: the contract holds for them after the permutation
+        keep = np.concatenate([s > 0, np.zeros((SWEEP_BATCH, ys.shape[2] - k), bool)], axis=1)
+        keep[~fin] = True
+        assert np.array_equal(np.where(keep[:, None, :], bits(yp), 0), np.where(keep[:, None, :], bits(ys), 0))
+        contract(up, np.take_along_axis(su, perm, axis=1), vp, full)
+
+    # thin = the first k columns of full, bit for bit: the rotations do not depend on the form, and the completion of
+    # a column j < k sees only the columns before k in either
+    for sort in (True, False):
+        fu, fs, fv, fi = res[True, sort]
+        tu, ts, tv, ti = res[False, sort]
+        assert np.array_equal(bits(ts), bits(fs)) and np.array_equal(ti, fi)
+        assert np.array_equal(bits(tu), bits(fu[:, :, :k])) and np.array_equal(bits(tv), bits(fv[:, :, :k]))
+
+
 # ------------------------------------------------------------------------------------------------------ determinism
 @pytest.mark.parametrize("m,n", [(20, 3), (3, 20), (7, 5), (17, 31), (32, 32)])
 def test_bitwise_reproducible_and_independent_of_the_batch(cuda, m, n):
@@ -187,6 +277,54 @@ def test_matrices_that_exhaust_max_sweeps_still_meet_the_contract(cuda, m, n, ba
         check_contract(a[stuck], u[stuck], s[stuck], v[stuck], True)
     some = np.flatnonzero(~stuck)[:2000]
     check_contract(a[some], u[some], s[some], v[some], True)
+
+
+# ------------------------------------------------------------------------------------------------------ large batches
+def tiled_pattern(rng, m, n):
+    """40 distinct matrices, one of them with a NaN"""
+    p = np.concatenate([gaussian(rng, 36, m, n), graded(rng, 1, m, n), np.zeros((1, m, n), np.float32),
+                        (np.eye(m, n) * 1.5)[None].astype(np.float32), gaussian(rng, 1, m, n)])
+    p[-1, m // 2, n // 2] = np.nan
+    return p
+
+
+@pytest.mark.parametrize("m,n,full,batch", [(9, 1, False, (1 << 28) + 37), (17, 17, True, (1 << 23) + 37)],
+                         ids=["lane", "cols"])
+def test_batch_past_the_block_cap_and_2_31_elements(cuda, m, n, full, batch):
+    """The launches cap the grid at 1 << 20 blocks and loop (64-bit offsets, a grid-stride loop for
+    any batch).  lane: 2^20 blocks of 256 matrices, 37 matrices in a second iteration, i m n up to 2.4e9.  cols
+    (G = 32, 8 matrices a block): 37 matrices in a second iteration of partial blocks, 2.4e9 elements.  Every matrix
+    of a batch tiled from 40 must equal that matrix's solo result bit for bit."""
+    k = min(m, n)
+    words = m * n + m * (m if full else k) + n * (n if full else k) + k + 1
+    need = batch * words * 4
+    torch.cuda.empty_cache()
+    free = torch.cuda.mem_get_info(cuda)[0]
+    if free < 1.5 * need:
+        pytest.skip("needs 1.5 x %.1f GB of free device memory, %.1f GB free" % (need / 1e9, free / 1e9))
+    pattern = torch.from_numpy(tiled_pattern(np.random.default_rng(m * 100 + n), m, n)).to(cuda)
+    period = pattern.shape[0]
+    solo = _linalg().batch_svd_forward(pattern, True, 1e-7, 100, return_info=True, full=full)
+    reps = batch // period
+    a = got = x = c = None
+    try:
+        a = torch.empty(batch, m, n, device=cuda)
+        a[:reps * period].view(reps, period, m, n).copy_(pattern)
+        a[reps * period:].copy_(pattern[:batch - reps * period])
+        got = _linalg().batch_svd_forward(a, True, 1e-7, 100, return_info=True, full=full)
+        del a
+        for x, y in zip(got, solo):
+            x = x.view(torch.int32).view(batch, -1)
+            y = y.view(torch.int32).view(period, -1)
+            rows = period * max(1, (1 << 28) // (period * x.shape[1]))     # rows per comparison, whole periods
+            for lo in range(0, batch, rows):
+                c = x[lo:lo + rows]
+                whole = c.shape[0] // period
+                assert bool((c[:whole * period].view(whole, period, -1) == y).all()), lo
+                assert bool((c[whole * period:] == y[:c.shape[0] - whole * period]).all()), lo
+    finally:
+        a = got = x = c = None          # nothing of this test's 20-30 GB outlives it, a failure's traceback included
+        torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------------------------ range

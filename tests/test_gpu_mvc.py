@@ -10,6 +10,7 @@ gradient and 1e-3 for the vertex gradient (measured up to 5e-6 and 1.6e-4, where
 cage); the vertex gradient of the interior queries alone within 1e-8; gradcheck pins the backward itself.  Fixture rows the reference decides by rounding (its
 fp64 row moves under a translation of the scene by 1e-9: ``stable`` False) are held to the weaker checks named where
 they are used (DESIGN.md "Mean value coordinates")."""
+import functools
 import glob
 import os
 import subprocess
@@ -231,6 +232,82 @@ def test_bitwise_reproducible(cuda, dtype, det_mode):
     for bi, pi in ((0, 0), (1, 2049), (2, 4096)):
         one = run(q[bi:bi + 1, pi:pi + 1], v[bi:bi + 1], f[bi:bi + 1])
         assert np.array_equal(one[0][0, 0], a[0][bi, pi]) and np.array_equal(one[1][0, 0], a[1][bi, pi])
+
+
+# --------------------------------------------------------------------------------------------- LDS and global paths
+# mvc.hip keeps a tile's accumulators in LDS while they fit: N * 65 * sizeof(T) bytes in the forward, N * 68 *
+# sizeof(T) in the backward (fwd_lds, bwd_lds); above 64 KiB the launch needs the big-LDS attribute, above kMaxLds =
+# 160 KiB the kernels take the global-memory path (the backward's with a zero-filled workspace).  Padding the ico1 cage
+# with isolated vertices far away moves N across each threshold without changing any (query, face) pair.
+def lds_thresholds(elem):
+    ns = set()
+    for words in (65, 68):
+        for cap in (64 << 10, 160 << 10):
+            last = cap // (words * elem)          # the largest N that fits
+            ns |= {last, last + 1}
+    return ns
+
+
+PATH_N = sorted(lds_thresholds(4) | lds_thresholds(8) | {2600})
+PATH_CAGE_N, PATH_P = 42, 4097                    # ico1; 65 tiles of 64 queries, the last one partial
+
+
+@functools.lru_cache(maxsize=None)
+def path_set():
+    """ico1, B = 3, P = 4097: the random queries of test_random_sets("ico1", 3, 4097) with the first 242 of each batch
+    element replaced by the 42 vertices, the 80 face centroids and the 120 edge midpoints of its cage"""
+    q, v, f, _, _ = random_set("ico1", 3, PATH_P, seed=3 * 10007 + PATH_P)
+    f0 = f[0].numpy()
+    edges = np.unique(np.sort(np.concatenate([f0[:, [0, 1]], f0[:, [1, 2]], f0[:, [2, 0]]]), axis=1), axis=0)
+    assert v.shape[1] == PATH_CAGE_N and len(f0) == 80 and len(edges) == 120
+    for b in range(3):
+        vb = v[b].astype(np.float64)
+        special = np.concatenate([vb, vb[f0].mean(1), vb[edges].mean(1)]).astype(np.float32)
+        q[b, :len(special)] = special
+    return q, v, f0
+
+
+def path_faces(dev, faces):
+    """the one face list of path_set on ``dev``: a batch-expanded view (faces_batch_stride 0) or one copy per batch
+    element (stride 3 F).  Expanded on the device: ``.to`` would materialise an expanded tensor."""
+    f = torch.from_numpy(path_set()[2]).to(dev)[None].expand(3, -1, -1)
+    return f.contiguous() if faces == "per_batch" else f
+
+
+@functools.lru_cache(maxsize=None)
+def path_baseline(dev, dtype):
+    """cotangents for the largest N (the first 42 columns are the unpadded run's) and the unpadded run itself"""
+    q, v, f0 = path_set()
+    gen = torch.Generator(device=dev).manual_seed(17)
+    G = torch.randn(3, PATH_P, max(PATH_N), dtype=dtype, device=dev, generator=gen)
+    Gwi = torch.randn(3, PATH_P, len(f0), 3, dtype=dtype, device=dev, generator=gen)
+    q, v = torch.from_numpy(q).to(dev, dtype), torch.from_numpy(v).to(dev, dtype)
+    return G, Gwi, run(q, v, path_faces(dev, "expanded"), G[..., :PATH_CAGE_N], Gwi=Gwi)
+
+
+def same_bits(x, y):
+    it = {4: np.int32, 8: np.int64}[x.dtype.itemsize]
+    return x.shape == y.shape and np.array_equal(np.ascontiguousarray(x).view(it), np.ascontiguousarray(y).view(it))
+
+
+@pytest.mark.parametrize("faces", ["expanded", "per_batch"])
+@pytest.mark.parametrize("N", PATH_N)
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+def test_lds_and_global_paths_are_bitwise_equal(cuda, dtype, N, faces):
+    """Every query row is the same bits on the LDS and the global path (mvc.hip's header): the cage padded to N
+    vertices gives the unpadded run's wj, wi and both gradients, and zeros for the isolated vertices.  The unpadded
+    run's random queries are held to the fp64 composition by test_random_sets("ico1", 3, 4097)."""
+    q, v, _ = path_set()
+    G, Gwi, (wj0, wi0, gq0, gv0) = path_baseline(cuda, dtype)
+    far = np.stack([50.0 + 0.5 * np.arange(N - PATH_CAGE_N), np.full(N - PATH_CAGE_N, -40.0),
+                    np.full(N - PATH_CAGE_N, 30.0)], axis=1)
+    vp = np.concatenate([v, np.broadcast_to(far, (3,) + far.shape)], axis=1)
+    wj, wi, gq, gv = run(torch.from_numpy(q).to(cuda, dtype), torch.from_numpy(vp).to(cuda, dtype),
+                         path_faces(cuda, faces), G[..., :N], Gwi=Gwi)
+    assert same_bits(wj[..., :PATH_CAGE_N], wj0) and (wj[..., PATH_CAGE_N:] == 0).all()
+    assert same_bits(wi, wi0)
+    assert same_bits(gq, gq0)
+    assert same_bits(gv[:, :PATH_CAGE_N], gv0) and (gv[:, PATH_CAGE_N:] == 0).all()
 
 
 # --------------------------------------------------------------------------------------------- memory

@@ -57,6 +57,27 @@ def test_workspace_query_and_argument_checks_are_host_only():
                                    None) != 0
 
 
+def row_error(got, ref, shape):
+    """max |got - ref| per query row, NaN where both are NaN counted as equal"""
+    err = np.abs(got - ref)
+    err[np.isnan(got) & np.isnan(ref)] = 0.0
+    return np.nan_to_num(err, nan=np.inf).reshape(shape + (-1,)).max(-1)
+
+
+def check_rows(wj, wi, z):
+    """wj / wi against the reference's fp64 rows to 1e-12; returns the rows that agree.  The composition is the
+    reference's chain of torch operations, but LAPACK's LU behind torch.linalg.det rounds differently on different
+    CPUs (MKL picks its code path by CPU), and a row the reference decides by rounding (``stable`` False: it moves
+    under a 1e-9 translation of the scene) can take the other branch there: such a row is held only to be finite
+    wherever the reference's is.  Every stable row agrees."""
+    st = z["stable"]
+    same = (row_error(wj, z["wj64"], st.shape) <= 1e-12) & (row_error(wi, z["wi64"], st.shape) <= 1e-12)
+    assert same[st].all(), np.argwhere(st & ~same)
+    assert np.isfinite(wj[~same][np.isfinite(z["wj64"][~same])]).all()
+    assert np.isfinite(wi[~same][np.isfinite(z["wi64"][~same])]).all()
+    return same
+
+
 @pytest.mark.parametrize("path", GOLDEN, ids=lambda p: os.path.basename(p)[4:-4])
 def test_composition_matches_reference_fp64(path):
     from pytorch_points_amd import mvc
@@ -64,12 +85,14 @@ def test_composition_matches_reference_fp64(path):
     q = torch.tensor(z["query"], dtype=torch.float64, requires_grad=True)
     v = torch.tensor(z["vertices"], dtype=torch.float64, requires_grad=True)
     wj, wi = mvc.composition(q, v, faces, verbose=True)
-    np.testing.assert_allclose(wj.detach().numpy(), z["wj64"], rtol=0, atol=1e-12)
-    np.testing.assert_allclose(wi.detach().numpy(), z["wi64"], rtol=0, atol=1e-12)
+    same = check_rows(wj.detach().numpy(), wi.detach().numpy(), z)
     gq, gv = torch.autograd.grad((wj * torch.from_numpy(z["G"])).sum(), (q, v))
     gq, gv = gq.numpy(), gv.numpy()
     assert np.isfinite(gq).all() and np.isfinite(gv).all()
-    for got, ref in ((gq, z["gq64"]), (gv, z["gv64"])):
+    # the gradients of the rows that agree: the query gradient of such a row, the vertex gradient of a batch element
+    # whose rows all agree (on the CPU the fixtures were recorded on: every row, every batch element)
+    whole = same.all(1)
+    for got, ref in ((gq[same], z["gq64"][same]), (gv[whole], z["gv64"][whole])):
         fin = np.isfinite(ref)
         np.testing.assert_allclose(got[fin], ref[fin], rtol=1e-9, atol=1e-9 * np.abs(ref[fin]).max(initial=1.0))
     assert (gq[z["kind"] == VERTEX] == 0).all()
@@ -97,10 +120,13 @@ def test_composition_fp32_and_other_dtypes_run():
         if tol:
             stable = z["stable"]
             np.testing.assert_allclose(wj.numpy()[stable], z["wj32"][stable], rtol=0, atol=tol)
-    # int32 faces are accepted too
-    wj = mean_value_coordinates_3D(torch.from_numpy(z["query"]).double(), torch.from_numpy(z["vertices"]).double(),
-                                   faces.int())
-    np.testing.assert_allclose(wj.numpy(), z["wj64"], atol=1e-12)
+    # int32 faces are accepted too, and give the int64 faces' result
+    from pytorch_points_amd import mvc
+    q, v = torch.from_numpy(z["query"]).double(), torch.from_numpy(z["vertices"]).double()
+    wj = mean_value_coordinates_3D(q, v, faces.int())
+    wj64, wi64 = mvc.composition(q, v, faces, verbose=True)
+    assert torch.equal(wj, wj64)
+    check_rows(wj.numpy(), wi64.numpy(), z)
 
 
 def test_composition_edge_sizes_and_bad_indices():
