@@ -320,6 +320,35 @@ int pp_mvc3d_backward_f64(const double* query, const double* vertices, const lon
                           const double* grad_wj, const double* grad_wi, double* grad_query, double* grad_vertices,
                           int B, int P, int N, int F, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Green coordinates --------------------------------------------------------------------
+ * Replaces network.geo_operations.green_coordinates_3D(query, vertices, faces, face_normals) (geo_operations.py:625-773,
+ * torch composition) for the pair evaluation; contract in DESIGN.md "Green coordinates".  query (B,P,3), vertices
+ * (B,N,3), faces int64 (B,F,3) read at faces + b * faces_batch_stride (elements; 0 = one face list for every batch
+ * element), normals (B,F,3) the face normals n_t.  Forward -> gc_vertex (B,P,N) normalised vertex coordinates,
+ * gc_face (B,P,F) face coordinates, sums (B,P) the unnormalised row sum S (exterior_flag = S < 0.5), codes (B,P) int32
+ * (8: an out-of-range face index in the batch element; its rows and sums are NaN).  Backward: grad_gc_vertex (B,P,N),
+ * grad_gc_face (nullable) -> grad_query (B,P,3), grad_normals (B,F,3), with a workspace of
+ * pp_gc3d_workspace_bytes(B,P,F,sizeof element) bytes.  The vertices get no gradient here (the reference detaches
+ * them).  No floating-point atomics: every output is reproducible bit for bit, and a query's row does not depend on
+ * the other queries. */
+size_t pp_gc3d_workspace_bytes(int B, int P, int F, int elem_bytes);
+int pp_gc3d_forward_f32(const float* query, const float* vertices, const long long* faces,
+                        long long faces_batch_stride, const float* normals, float* gc_vertex, float* gc_face,
+                        float* sums, int* codes, int B, int P, int N, int F, void* stream);
+int pp_gc3d_forward_f64(const double* query, const double* vertices, const long long* faces,
+                        long long faces_batch_stride, const double* normals, double* gc_vertex, double* gc_face,
+                        double* sums, int* codes, int B, int P, int N, int F, void* stream);
+int pp_gc3d_backward_f32(const float* query, const float* vertices, const long long* faces,
+                         long long faces_batch_stride, const float* normals, const float* gc_vertex,
+                         const float* sums, const int* codes, const float* grad_gc_vertex, const float* grad_gc_face,
+                         float* grad_query, float* grad_normals, int B, int P, int N, int F, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int pp_gc3d_backward_f64(const double* query, const double* vertices, const long long* faces,
+                         long long faces_batch_stride, const double* normals, const double* gc_vertex,
+                         const double* sums, const int* codes, const double* grad_gc_vertex,
+                         const double* grad_gc_face, double* grad_query, double* grad_normals, int B, int P, int N,
+                         int F, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

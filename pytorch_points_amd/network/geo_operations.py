@@ -1,9 +1,11 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
 furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
-(:88-126) and the cage coordinates mean_value_coordinates_3D (:349-456).  The other mesh-geometry functions of that
-file are out of scope."""
+(:88-126), the cage coordinates mean_value_coordinates_3D (:349-456) and green_coordinates_3D (:625-773), and the
+face normals those need, compute_face_normals_and_areas (:529-559).  The other mesh-geometry functions of that file
+are out of scope."""
 import torch
 
+from .. import green as _green
 from .. import mvc as _mvc
 from .. import ops
 from .._ext import sampling
@@ -109,3 +111,18 @@ def mean_value_coordinates_3D(query, vertices, faces, verbose=False):
     per-face weights.  CUDA fp32 / fp64 run fused HIP kernels; other devices and dtypes a torch composition of the
     same contract (pytorch_points_amd.mvc, DESIGN.md "Mean value coordinates")."""
     return _mvc.mean_value_coordinates_3D(query, vertices, faces, verbose)
+
+
+def compute_face_normals_and_areas(vertices, faces):
+    """``(face_normals (B,F,3), face_areas (B,F))`` of the triangles ``faces`` over ``vertices`` (B,N,3); 2-D inputs
+    give unbatched outputs (pytorch_points_amd.green)."""
+    return _green.compute_face_normals_and_areas(vertices, faces)
+
+
+def green_coordinates_3D(query, vertices, faces, face_normals=None, verbose=False):
+    """Green coordinates (Lipman et al. 2008) of ``query`` (B,P,3) with respect to the closed triangle cage
+    ``vertices`` (B,N,3), ``faces`` (B,F,3): ``(GC_vertex (B,P,N), GC_face (B,P,F), exterior_flag (B,P,1))``.
+    ``face_normals`` (B,F,3) replaces the normals computed from the cage; ``verbose`` is ignored.  CUDA fp32 / fp64
+    run fused HIP kernels; other devices and dtypes a torch composition of the same contract
+    (pytorch_points_amd.green, DESIGN.md "Green coordinates")."""
+    return _green.green_coordinates_3D(query, vertices, faces, face_normals, verbose)
