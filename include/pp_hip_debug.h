@@ -19,12 +19,9 @@ extern "C" {
 void pp_debug_set_nmdistance_search(int mode);
 /* brute-force kernel variant (Q queries per lane, G points per group, packed / prefetch forms; chamfer.hip) */
 void pp_debug_set_nmdistance_variant(int variant);
-/* grid search, wave-private form of the search kernel: staged points per wave (320, 384, 512; selecting one also
- * selects that form; 0 = the default, the tile form) */
-void pp_debug_set_nmdistance_stage_cap(int points);
-/* grid search, unlabeled: queries per workgroup of the stage-A kernel (0 = 512; 256, 1024); -1 = no stage-A kernel.
- * The same values are read once from the environment variable PP_NMDISTANCE_TILE when the knob is 0. */
-void pp_debug_set_nmdistance_tile(int queries);
+/* grid search, unlabeled: 0 = the stage-A kernel, then the list kernel over what it left (default; any other value
+ * means this too); -1 = no stage-A kernel, the whole-search kernel serves every query */
+void pp_debug_set_nmdistance_tile(int mode);
 /* grid search, unlabeled: the build of sets of at most 16384 aligned points: 0 = sorted through the LDS, a slab owning
  * whole z-layers (default), 1 = the general build always (tests and A/B timing) */
 void pp_debug_set_nmdistance_build(int general);
@@ -39,10 +36,9 @@ void pp_debug_set_nmdistance_row_bitmap(int off);
 void pp_debug_set_labeled_variant(int variant);
 /* Chamfer backward: 1 LDS doubles, 2 CSR lists, 3 LDS fp32 columns, 4 global atomics, 5 deterministic */
 void pp_debug_set_nmdistance_backward_variant(int variant);
-/* per-kernel HIP-event timing of the grid forward (build, search), read back after the call */
+/* per-kernel HIP-event timing of the grid forward, read back after the call: the build and the search's two launches
+ * (stage A by tiles, then what it left); stage_a_ms = 0 without a stage-A kernel */
 void pp_debug_set_nmdistance_kernel_timing(int on);
-int pp_debug_nmdistance_kernel_ms(float* build_ms, float* search_ms);
-/* the same with the search's two launches apart (stage A by tiles, then what it left); stage_a_ms = 0 without a stage-A kernel */
 int pp_debug_nmdistance_kernel_ms3(float* build_ms, float* stage_a_ms, float* rest_ms);
 
 /* ... and the build's and the stage-A kernel's OWN durations of the most recent forward timed with the knob at 2 (the

@@ -29,7 +29,6 @@
 //         set whose grid is useless (non-finite coordinates).  Two launches per forward, no list.
 #include <algorithm>
 #include <hip/hip_ext.h>
-#include <cstdlib>
 #include <mutex>
 
 #ifdef PP_BUILD_PROBE
@@ -1810,10 +1809,11 @@ __device__ __forceinline__ float min2(float a, float b) {
 #else
 #define PP_SPHASE(n)
 #endif
+constexpr int CAPW = 384;  // points of a wave's private slice of LDS (both kernels that call search_queries)
 // W: the waves per SIMD the calling kernel is compiled for -- it only makes the out-of-line stages below separate
 // functions per kernel, each compiled for its caller's register budget (the list kernel runs at 5: 96 registers, no
 // spills in the group search; gaussian -8 %, blobs8 -6 %, disjoint -6 % against 6 waves and 80 registers)
-template <bool LAB, int CAPW, int W>
+template <bool LAB, int W>
 __device__ __forceinline__ void search_queries(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
                                                float* __restrict__ dist1, int* __restrict__ idx1,
                                                float* __restrict__ dist2, int* __restrict__ idx2,
@@ -2351,8 +2351,8 @@ __device__ __forceinline__ void search_queries(const float* __restrict__ xyz1, c
 
 // The whole search in one kernel (labeled searches; unlabeled ones when there is no stage-A kernel): 256-thread
 // workgroups of four independent waves, workgroup `tile` of (b, dir) takes queries [256 tile, 256 tile + 256).
-template <bool LAB, int CAPW>
-__global__ __launch_bounds__(256, LAB ? (CAPW > 384 ? 3 : 4) : (CAPW > 384 ? 4 : PP_WAVE_WAVES)) void grid_query_wave_kernel(
+template <bool LAB>
+__global__ __launch_bounds__(256, LAB ? 4 : PP_WAVE_WAVES) void grid_query_wave_kernel(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, float* __restrict__ dist1, int* __restrict__ idx1,
     float* __restrict__ dist2, int* __restrict__ idx2, unsigned char* __restrict__ ws, int B, int N, int M, int tiles1,
     int tiles2, int total, int per_xcd, const float* __restrict__ label1, const float* __restrict__ label2) {
@@ -2372,7 +2372,7 @@ __global__ __launch_bounds__(256, LAB ? (CAPW > 384 ? 3 : 4) : (CAPW > 384 ? 4 :
   __shared__ pp::f4 s_pts[4][CAPW + 4];
   __shared__ float s_lab[4][LAB ? CAPW + 4 : 1];
   const int wave = pp::wave_id_uniform();
-  search_queries<LAB, CAPW, (LAB ? (CAPW > 384 ? 3 : 4) : (CAPW > 384 ? 4 : PP_WAVE_WAVES))>(xyz1, xyz2, dist1, idx1, dist2, idx2, ws, B, N, M, label1, label2, L, b, dir, jj, valid, false,
+  search_queries<LAB, (LAB ? 4 : PP_WAVE_WAVES)>(xyz1, xyz2, dist1, idx1, dist2, idx2, ws, B, N, M, label1, label2, L, b, dir, jj, valid, false,
                             (lds_f4_wptr)(&s_pts[wave][0]), (lds_f_wptr)(&s_lab[wave][0]));
 }
 
@@ -2395,11 +2395,13 @@ constexpr int kPendTried = 1 << 30;
                             // 0.440 ms, 1: the same with the sphere's empty launch +1 %, 8 / 16: 0.49 / 0.62)
 #endif
 constexpr int kListWgWaves = PP_LIST_WG_WAVES;
+// the stage-A kernel (below): queries per tile = threads per workgroup, points of a tile's LDS image at most, and the
+// waves per SIMD it is compiled for
+constexpr int kTileQ = 512, kTileCap = 3260, kTileWaves = 6;
 #ifndef PP_LIST_RIM_UNITS
 #define PP_LIST_RIM_UNITS 4
 #endif
 constexpr int kListRimUnits = PP_LIST_RIM_UNITS;  // workgroups from either end of a set's tiles that the launch starts first
-template <int CAPW>
 __global__ __launch_bounds__(64 * kListWgWaves, PP_LIST_WAVES) void grid_query_list_kernel(const float* __restrict__ xyz1,
                                                                   const float* __restrict__ xyz2,
                                                                   float* __restrict__ dist1, int* __restrict__ idx1,
@@ -2531,7 +2533,7 @@ __global__ __launch_bounds__(64 * kListWgWaves, PP_LIST_WAVES) void grid_query_l
       __builtin_amdgcn_wave_barrier();  // (the slice is the search's from here on)
       skip_a = __all(!valid || (entry & kPendTried) != 0);
     }
-    search_queries<false, CAPW, PP_LIST_WAVES>(xyz1, xyz2, dist1, idx1, dist2, idx2, ws, B, N, M, nullptr, nullptr, L, b, dir,
+    search_queries<false, PP_LIST_WAVES>(xyz1, xyz2, dist1, idx1, dist2, idx2, ws, B, N, M, nullptr, nullptr, L, b, dir,
                                 entry & ~kPendTried, valid, skip_a, (lds_f4_wptr)(&s_pts[wave][0]), (lds_f_wptr) nullptr,
                                 rowbits != nullptr ? rowbits + (size_t)set * 32 : nullptr);
   }
@@ -2541,12 +2543,12 @@ __global__ __launch_bounds__(64 * kListWgWaves, PP_LIST_WAVES) void grid_query_l
 // Round 3: stage A as a kernel of its own (unlabeled searches; the kernel above, in LIST mode, then serves what it
 // leaves).  Why: inside one kernel the rare long tails -- a wave with leftover queries runs the whole-wave cubes for
 // microseconds -- held back the LDS of their whole workgroup, and the tails' registers (80) capped the occupancy of
-// the 99.7 % of the work that never needs them.  Here a workgroup is a TILE of TQ consecutive queries of the sorted
+// the 99.7 % of the work that never needs them.  Here a workgroup is a TILE of kTileQ consecutive queries of the sorted
 // query cloud:
 //   * the z-layers of the reference grid its queries' 2x2x2 blocks can touch come from the QUERY cloud's chunk table
 //     (grid_common.h: kChunk; two scalar loads per build slab and chunk -- no reduction over the tile, nothing waits
 //     for the queries themselves); those layers are ONE contiguous piece of the sorted reference cloud (cells are
-//     z-major), copied into ONE LDS image of at most CAP points shared by the tile's waves, while the lanes' own
+//     z-major), copied into ONE LDS image of at most kTileCap points shared by the tile's waves, while the lanes' own
 //     queries and the bounds of their blocks' rows are still on their way; one workgroup barrier;
 //   * every lane walks the four rows of its block in the image -- one sequence of groups of four consecutive points,
 //     only the running minimum (v_min3) and the byte position of the group that last lowered it tracked; the winner's
@@ -2554,7 +2556,7 @@ __global__ __launch_bounds__(64 * kListWgWaves, PP_LIST_WAVES) void grid_query_l
 //     (distance, index) order -- and is settled if its best distance is below what the block guarantees (reach);
 //   * settled queries store their result; the others are written to the wave's 64 slots of the pending list with the
 //     wave's count (no atomics).  A tile that cannot be served this way (sets with crowded cells, degenerate sets,
-//     images beyond CAP, no chunk table) leaves ALL its queries pending: same results either way.
+//     images beyond kTileCap, no chunk table) leaves ALL its queries pending: same results either way.
 // Same candidates, same arithmetic (pp::chamfer_d3), same tie rule as the kernel above.
 __device__ __forceinline__ unsigned lean_group_pos(unsigned k, unsigned T1, unsigned T2, unsigned T3, unsigned a0,
                                                    unsigned a1, unsigned a2, unsigned a3, unsigned endb) {
@@ -2570,23 +2572,20 @@ typedef const char __attribute__((address_space(3))) * lds_c_ptr;
 #else
 #define PP_APHASE(n)
 #endif
-// What a tile's front needs from memory, ordered in ONE round trip and a tile AHEAD (the kernel is persistent: a
-// workgroup walks tile i while this is on its way for tile i + 1): lanes 0..47 of `meta` = the reference grid's
-// descriptor (16 words), the query grid's (16), the tile's chunk-table entries (<= 16 words for TQ <= 512; 32 at 1024:
-// meta2); `lay` = the reference grid's layer table (lane z: first point of layer z); `qq` = the lane's query.
-template <int TQ>
+// What a tile's front needs from memory, ordered in ONE round trip: lanes 0..47 of `meta` = the reference grid's
+// descriptor (16 words), the query grid's (16), the tile's chunk-table entries (16 words: eight per chunk);
+// `lay` = the reference grid's layer table (lane z: first point of layer z); `qq` = the lane's query.
 struct StageAFront {
   int live;             // the virtual tile exists (the grid is padded to a multiple of eight)
   int b, dir, tile, jj;
   bool valid;
-  unsigned meta, meta2, lay;
+  unsigned meta, lay;
   pp::f4 qq;
 };
-template <int TQ>
-__device__ __forceinline__ void stage_a_issue(StageAFront<TQ>& f, int it, int per_xcd, int total, int tiles1, int tiles2,
+__device__ __forceinline__ void stage_a_issue(StageAFront& f, int vb, int per_xcd, int total, int tiles1, int tiles2,
                                               int N, int M, const unsigned char* __restrict__ ws, const Layout& L, int t,
                                               int lane) {
-  const int V = pp::xcd_virtual_block(it, per_xcd);
+  const int V = pp::xcd_virtual_block(vb, per_xcd);
   f.live = V < total ? 1 : 0;
   const int Vc = f.live ? V : 0;  // (a padding tile loads tile 0's front and does nothing with it)
   const int per_b = tiles1 + tiles2;
@@ -2595,44 +2594,39 @@ __device__ __forceinline__ void stage_a_issue(StageAFront<TQ>& f, int it, int pe
   f.dir = r >= tiles1 ? 1 : 0;
   f.tile = f.dir ? r - tiles1 : r;
   const int nq = f.dir ? M : N;
-  f.valid = f.live && f.tile * TQ + t < nq;
-  f.jj = f.valid ? f.tile * TQ + t : nq - 1;
+  f.valid = f.live && f.tile * kTileQ + t < nq;
+  f.jj = f.valid ? f.tile * kTileQ + t : nq - 1;
   const int set = 2 * f.b + f.dir;
-  constexpr int kTz = 8 * (TQ / pp::kChunk);  // chunk-table words of a tile
-  static_assert(pp::kBuildSlabs == 4 && kTz <= 32, "eight words per chunk");
+  constexpr int kTz = 8 * (kTileQ / pp::kChunk);  // chunk-table words of a tile
+  static_assert(pp::kBuildSlabs == 4 && kTz <= 16, "eight words per chunk, lanes 32..47 of meta");
   const unsigned* __restrict__ gsets = reinterpret_cast<const unsigned*>(ws + L.sets);
   const unsigned* __restrict__ tz = reinterpret_cast<const unsigned*>(ws + L.tile_z) +
-                                    ((size_t)(set ^ 1) * L.chunks + (size_t)f.tile * (TQ / pp::kChunk)) * 8;
+                                    ((size_t)(set ^ 1) * L.chunks + (size_t)f.tile * (kTileQ / pp::kChunk)) * 8;
   const unsigned* __restrict__ src = lane < 16 ? gsets + 16 * (size_t)set + lane
                                                : (lane < 32 ? gsets + 16 * (size_t)(set ^ 1) + (lane - 16)
                                                             : tz + min(lane - 32, kTz - 1));
   f.meta = *src;
-  f.meta2 = kTz > 16 ? tz[min(lane, kTz - 1)] : 0u;
   f.lay = (reinterpret_cast<const unsigned*>(ws + L.layers) + (size_t)set * pp::kLayerWords)[lane < pp::kLayerWords ? lane : 0];
   const pp::f4* __restrict__ qsorted = reinterpret_cast<const pp::f4*>(ws + L.sorted) + set_point_offset(f.b, f.dir ^ 1, N, M);
   // (an asm load: a plain one the compiler sinks to its first use, a round trip later; it is invisible to the compiler's
-  //  counting of loads in flight, so an explicit s_waitcnt vmcnt(0) precedes every use -- stage_a_kernel's loop top)
+  //  counting of loads in flight, so an explicit s_waitcnt vmcnt(0) precedes every use -- grid_stage_a_kernel's top)
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(f.qq) : "v"((unsigned)f.jj << 4), "s"(qsorted) : "memory");
 }
 
-template <int TQ, int CAP, int WPE, bool PERSIST>
-__global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict__ dist1, int* __restrict__ idx1,
+__global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float* __restrict__ dist1, int* __restrict__ idx1,
                                                               float* __restrict__ dist2, int* __restrict__ idx2,
                                                               unsigned char* __restrict__ ws, int B, int N, int M,
                                                               int tiles1, int tiles2, int total, int per_xcd,
                                                               const Layout L, unsigned* __restrict__ routed_host,
                                                               unsigned epoch, const unsigned* __restrict__ pre_routed) {
-  static_assert(TQ % pp::kChunk == 0 && (CAP + 63) / 64 * 64 + 4 <= 4096 + 4, "");
-  // PERSISTENT: the launch is a few workgroups per CU (a multiple of eight, so that a workgroup's tiles stay on its
-  // XCD under the round-robin placement -- speed only); workgroup w takes the virtual tiles w, w + gridDim.x, ...
-  const int nvt = per_xcd * 8;
+  static_assert(kTileQ % pp::kChunk == 0 && (kTileCap + 63) / 64 * 64 + 4 <= 4096 + 4, "");
   const int t = threadIdx.x, lane = t & 63;
   const int wave = pp::wave_id_uniform();
   // (the per-direction workgroups come FIRST in the launch -- 2 B of them rounded up to a multiple of eight, so that the
   //  tiles keep their XCDs: behind the tiles they started last and a launch whose tiles all decline waited 2-3 us for them)
-  const int head = PERSIST ? 0 : (2 * B + 7) / 8 * 8;
+  const int head = (2 * B + 7) / 8 * 8;
   const int bid = (int)blockIdx.x - head;  // the tile's workgroup
-  if (!PERSIST && bid < 0) {
+  if (bid < 0) {
     // Round 6: 2 B workgroups behind the tiles' (dispatched last, into the launch's tail), one per direction: is this
     // a direction no search can prune (direction_unprunable, on samples of the sorted clouds)?  Then the host is told
     // (routed_host): from its next calls on the decision is taken in front of the build (route_decide_kernel) and the
@@ -2652,7 +2646,7 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
       //  lookups touch every line of the cell table, 4.5 MB over the 64 sets of config 2, and an evenly sampled surface
       //  never gets to the group search: its words say "every row", which the search reads as "no bitmap")
       const bool wanted = pp::grid_refined(g);
-      for (int r0 = wave * 64; r0 < pp::kGridMax * pp::kGridMax; r0 += TQ) {  // (wave-uniform)
+      for (int r0 = wave * 64; r0 < pp::kGridMax * pp::kGridMax; r0 += kTileQ) {  // (wave-uniform)
         const int r = r0 + lane;
         const bool ne = !wanted || (r < nall && cs[(r + 1) * gx] != cs[r * gx]);
         const unsigned long long bal = __ballot(ne);
@@ -2678,26 +2672,27 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
     }
     return;
   }
-  constexpr int kW = TQ / 64;
+  constexpr int kW = kTileQ / 64;
   constexpr int kQueue = 64;  // leftovers of a tile served from the image (more than that stay for the list kernel)
-  __shared__ pp::f4 s_img[(CAP + 63) / 64 * 64 + 4];  // (whole pieces of 64 points, then the padding)
+  __shared__ pp::f4 s_img[(kTileCap + 63) / 64 * 64 + 4];  // (whole pieces of 64 points, then the padding)
   __shared__ pp::f4 s_queue[kQueue];
   __shared__ unsigned s_qres[kQueue];
   __shared__ unsigned s_qn;
   __shared__ unsigned s_tot;  // queries of the tile left pending
   PP_QPHASE_DECL;
-  StageAFront<TQ> nx;
-  stage_a_issue<TQ>(nx, bid, per_xcd, total, tiles1, tiles2, N, M, ws, L, t, lane);
-  // A tile's results are stored at the top of the NEXT iteration, behind that iteration's wait for its front: the
-  // wait below must be vmcnt(0) (the asm load), and scattered 4-byte stores issued just before it would make every
-  // tile wait for them to retire.
+  StageAFront f;
+  stage_a_issue(f, bid, per_xcd, total, tiles1, tiles2, N, M, ws, L, t, lane);
+  // The tile's body is the single pass of a loop, and a settled query's result is stored at the loop's top (never
+  // reached with a result) or behind it: the source shape of the kernel as it was measured.  Written straight-line,
+  // with the store where the result is computed or at the end, the same work compiles to other code (28 fewer
+  // instructions, two fewer registers, another allocation: NOTEBOOK.md, 2026-10-16) that has not been timed; so
+  // does a loop counted from 0.
   float sv_d = 0.0f;
   int sv_i = 0, sv_off = 0, sv_dir = 0;
   bool sv_ok = false;
-  // (!PERSIST: a workgroup per tile, the loop is one pass and the compiler knows it: no state lives across it)
-  for (int it = bid; it < (PERSIST ? nvt : bid + 1); it += (PERSIST ? (int)gridDim.x : 1)) {  // workgroup-uniform
+  for (int it = bid; it < bid + 1; ++it) {  // (one pass)
   PP_APHASE(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's front has landed (the asm load of the query too)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tile's front has landed (the asm load of the query too)
   if (sv_ok) {
     (sv_dir ? dist2 : dist1)[sv_off] = sv_d;
     (sv_dir ? idx2 : idx1)[sv_off] = sv_i;
@@ -2707,33 +2702,21 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
     s_qn = 0u;   // barrier behind the image's arrival -- or by the one a tile whose image does not fit meets instead
     s_tot = 0u;
   }
-  const StageAFront<TQ> f = nx;
-  if (PERSIST && it + (int)gridDim.x < nvt)  // the next tile's front goes out now and travels while this tile is walked
-    stage_a_issue<TQ>(nx, it + (int)gridDim.x, per_xcd, total, tiles1, tiles2, N, M, ws, L, t, lane);
   const int b = f.b, dir = f.dir, tile = f.tile, jj = f.jj;
   const bool valid = f.valid;
   const int nq = dir ? M : N;
   const int set = 2 * b + dir;
-  if (pre_routed != nullptr && f.live && pre_routed[set] != 0u) {  // (uniform over the direction) served by the every-pair kernel
-    if constexpr (PERSIST) {
-      __syncthreads();
-      continue;
-    } else {
-      return;
-    }
-  }
+  if (pre_routed != nullptr && f.live && pre_routed[set] != 0u) return;  // (uniform over the direction) served by the every-pair kernel
   const pp::f4 qq = f.qq;
   const unsigned lay = f.lay;
   auto meta = [&](int l) { return __builtin_amdgcn_readlane((int)f.meta, l); };
   int kmin = 0x7fffffff, kmax = (int)0x80000000;  // the tile's lowest / highest z (pp::zkey)
   {
-    constexpr int kTz = 8 * (TQ / pp::kChunk);
+    constexpr int kTz = 8 * (kTileQ / pp::kChunk);
 #pragma unroll
     for (int w = 0; w < kTz; w += 2) {
-      const int lo = kTz > 16 ? __builtin_amdgcn_readlane((int)f.meta2, w) : meta(32 + w);
-      const int hi = kTz > 16 ? __builtin_amdgcn_readlane((int)f.meta2, w + 1) : meta(32 + w + 1);
-      kmin = min(kmin, lo);
-      kmax = max(kmax, hi);
+      kmin = min(kmin, meta(32 + w));
+      kmax = max(kmax, meta(32 + w + 1));
     }
   }
   int* __restrict__ plist = reinterpret_cast<int*>(ws + L.pend) + set_point_offset(b, dir ^ 1, N, M);
@@ -2750,8 +2733,8 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
   // degenerate set, and the query cloud's chunk table exists; no short-circuits: nothing here is worth a branch
   const bool grids_ok = ((meta(8) | meta(12) | meta(13) | meta(14) | meta(15) | meta(16 + 8) | meta(16 + 12) | meta(16 + 13) |
                           meta(16 + 14) | meta(16 + 15) | (meta(16 + 10) ^ 1)) == 0);
-  // ... and the images of this direction's tiles are likely to fit: a tile of TQ queries spans about TQ gz / nq layers
-  // of the reference grid, its image those and three more (one straddled, one either side), each at most as full as
+  // ... and the images of this direction's tiles are likely to fit: a tile of kTileQ queries spans about
+  // kTileQ gz / nq layers of the reference grid, its image those and three more (one straddled, one either side), each at most as full as
   // the grid's fullest layer.  A volume-filling cloud (coarser grid, fuller layers), a plane (one layer) or a Gaussian
   // (its core) fails this, and its tiles would find their images too large one by one.
   // (the fullest layer counts, not the average: the core of a Gaussian, a face of a box)
@@ -2761,7 +2744,7 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
     const float sz = lane < g.gz ? (float)(nxt - lay) : 0.0f;  // (layer populations are < 2^24: exact)
     lmax = (unsigned)pp::wave_reduce_dpp<false>(sz);
   }
-  const bool fits = (long long)(3 + (TQ * g.gz + nq - 1) / nq) * (long long)lmax <= (long long)CAP;
+  const bool fits = (long long)(3 + (kTileQ * g.gz + nq - 1) / nq) * (long long)lmax <= (long long)kTileCap;
   if (f.live && !(grids_ok && fits)) {
     // (uniform over the direction) nothing of this direction is served here: its total is set to "every query" by the
     // first tile (no list is written: the list kernel then takes entry e to be query e) and the tile is done -- a
@@ -2773,12 +2756,7 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
     //  list kernel gained 10-40 us: cube 0.129 -> 0.199 ms, gaussian 0.226 -> 0.374)
     if (tile == 0 && t == 0)
       (reinterpret_cast<unsigned*>(ws + L.layers) + (size_t)set * pp::kLayerWords)[pp::kLayerPending] = (unsigned)nq;
-    if constexpr (PERSIST) {
-      __syncthreads();
-      continue;
-    } else {
-      return;
-    }
+    return;
   }
   const bool lean_ok = f.live != 0;
   if (lean_ok) {
@@ -2795,8 +2773,8 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
     const int Hz = min(__builtin_amdgcn_readfirstlane(cell_coord(pp::zkey_inv(kmax), g.minz, g.invh, g.gz)) + 1, gz1);
     const unsigned tb0 = (unsigned)__builtin_amdgcn_readlane((int)lay, Lz);
     const unsigned ns = (unsigned)__builtin_amdgcn_readlane((int)lay, Hz + 1) - tb0;
-    if (!(ns > 0u && ns <= (unsigned)CAP)) __syncthreads();  // (the counters above are zero before anyone adds to them)
-    if (ns > 0u && ns <= (unsigned)CAP) {  // workgroup-uniform
+    if (!(ns > 0u && ns <= (unsigned)kTileCap)) __syncthreads();  // (the counters above are zero before anyone adds to them)
+    if (ns > 0u && ns <= (unsigned)kTileCap) {  // workgroup-uniform
       // the image: [tb0, tb0 + ns) of the sorted cloud, by LDS-DMA (global_load_lds_dwordx4: no registers, no ds_write),
       // in pieces of 64 points, wave w the pieces w, w + kW, ...; ordered here, before anything waits.  A piece's lanes
       // beyond the image's end re-read its last point (the slots behind the end are the padding's, written below).
@@ -2939,7 +2917,7 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
       PP_APHASE(4);
       tried = kPendTried;
       if (valid && best < reach * reach * kBoundSlack) {  // settled (strict; a NaN bound settles nothing)
-        sv_ok = true;  // (stored at the top of the next iteration, or after the loop)
+        sv_ok = true;  // (stored behind the loop)
         sv_d = best;
         sv_i = bidx;
         sv_off = b * nq + __float_as_int(qq.w);  // (B * (N + M) < 2^31: grid_applicable)
@@ -3025,7 +3003,7 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
   }
   // what is left goes to the wave's slots of the pending list (in lane order: the order of the sorted cloud)
   const unsigned long long pm = __ballot(pend);
-  const int wq = tile * (TQ / 64) + wave;  // this wave among the waves of the direction
+  const int wq = tile * (kTileQ / 64) + wave;  // this wave among the waves of the direction
   if (f.live && wq * 64 < nq) {
     if (pend) plist[wq * 64 + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(pm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)pm, 0u))] = jj | tried;
     if (lane == 0) {
@@ -3034,12 +3012,12 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
     }
   }
   PP_APHASE(5);
-  __syncthreads();  // every wave has left the image: the next tile's may be written
+  __syncthreads();  // every wave's count is in s_tot
   // the direction's total (zeroed by the build), ONE global atomic per tile that leaves anything (a wave-by-wave
   // count -- 256 adds to one word per direction -- cost the kernel 5 us): lets the list kernel's waves leave at once
   if (t == 0 && s_tot != 0u)
     atomicAdd(reinterpret_cast<unsigned*>(ws + L.layers) + (size_t)set * pp::kLayerWords + pp::kLayerPending, s_tot);
-  }  // (tiles)
+  }
   if (sv_ok) {
     (sv_dir ? dist2 : dist1)[sv_off] = sv_d;
     (sv_dir ? idx2 : idx1)[sv_off] = sv_i;
@@ -3052,11 +3030,8 @@ __global__ __launch_bounds__(TQ, WPE) void grid_stage_a_kernel(float* __restrict
 // launches); 1 = brute force; 2 = grid wherever it is structurally possible (tests)
 static pp::Knob g_grid_mode;
 extern "C" void pp_debug_set_nmdistance_search(int v) { g_grid_mode.set(v); }
-// LDS points per wave of the whole-search kernel (grid_query_wave_kernel): 0 = default (384); 320 / 512 for comparison
-static pp::Knob g_stage_cap;
-extern "C" void pp_debug_set_nmdistance_stage_cap(int v) { g_stage_cap.set(v); }
-// unlabeled searches: queries per workgroup of the stage-A kernel: 0 = default (512); 256, 512, 1024; -1 = no stage-A
-// kernel (round 2's two launches: the whole-search kernel serves every query)
+// unlabeled searches: 0 = the stage-A kernel, then the list kernel (default; any other value means this too); -1 = no
+// stage-A kernel (round 2's two launches: the whole-search kernel serves every query)
 static pp::Knob g_tile;
 extern "C" void pp_debug_set_nmdistance_tile(int v) { g_tile.set(v); }
 // the build of config 2's class: 0 = the LDS-sorted path where it applies (default), 1 = the general path always
@@ -3065,7 +3040,7 @@ extern "C" void pp_debug_set_nmdistance_build(int v) { g_build_fast.set(v); }
 
 // Per-kernel timing of the grid forward (bench.py's roofline of the dominant kernel): when switched on, HIP
 // events are recorded on the launch stream before the build, between the two kernels and after the search;
-// pp_debug_nmdistance_kernel_ms waits for the last one and reports the two durations of the most recent
+// pp_debug_nmdistance_kernel_ms3 waits for the last one and reports the durations of the most recent
 // forward.  One set of events per process (a measurement aid for one stream at a time, not a product feature).
 static pp::Knob g_time_kernels;
 static std::mutex g_ev_mutex;
@@ -3073,14 +3048,6 @@ static hipEvent_t g_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // before the
 static bool g_ev_valid = false;
 static bool g_ev_two_stage = false;
 extern "C" void pp_debug_set_nmdistance_kernel_timing(int on) { g_time_kernels.set(on); }
-extern "C" int pp_debug_nmdistance_kernel_ms(float* build_ms, float* search_ms) {
-  std::lock_guard<std::mutex> lock(g_ev_mutex);
-  if (!g_ev_valid || !build_ms || !search_ms) return PP_EINVAL;
-  hipError_t e = hipEventSynchronize(g_ev[3]);
-  if (e == hipSuccess) e = hipEventElapsedTime(build_ms, g_ev[0], g_ev[1]);
-  if (e == hipSuccess) e = hipEventElapsedTime(search_ms, g_ev[1], g_ev[3]);
-  return (int)e;
-}
 // the search's two launches by themselves (unlabeled searches: the stage-A kernel, then the kernel that serves what it
 // left); stage_a_ms = 0 when the most recent forward had no stage-A kernel
 extern "C" int pp_debug_nmdistance_kernel_ms3(float* build_ms, float* stage_a_ms, float* rest_ms) {
@@ -3228,13 +3195,8 @@ static int grid_forward(const float* xyz1, const float* xyz2, const float* label
   if (e != hipSuccess) return (int)e;
   const bool timing = g_time_kernels != 0;
   if (timing) record_timing_event(0, s);
-  static const int tile_env = [] {
-    const char* e = getenv("PP_NMDISTANCE_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  const int tile = g_tile != 0 ? (int)g_tile : tile_env;
   const Layout lay = make_layout(B, N, M, LAB);
-  const bool two_stage = !LAB && tile != -1 && lay.chunks > 0;
+  const bool two_stage = !LAB && g_tile != -1 && lay.chunks > 0;
   // routing (see route_word above): while the host has not seen a routed direction lately, the stage-A launch's tail
   // tests every direction and tells the host; once it has, the test runs in front of the build (route_decide_kernel)
   // and the every-pair kernel serves the routed directions behind the list kernel
@@ -3283,68 +3245,35 @@ static int grid_forward(const float* xyz1, const float* xyz2, const float* label
   const long long blocks = (long long)B * (tiles1 + tiles2);
   if (blocks > 0x7fffffffLL) return PP_EINVAL;
   const int per_xcd = (int)((blocks + 7) / 8);
-  // (PP_NMDISTANCE_TILE: the debug knob's value from the environment, read once -- benchmarks of the forms in processes
-  //  that do not call the knob)
   if (two_stage) {  // stage A by tiles, then the whole-search kernel over what it left (LIST)
-    const int tq = tile == 256 || tile == 1024 || tile == 513 ? tile : 512;
-    const int tqq = tq == 513 ? 512 : tq;
-    const int ta1 = (N + tqq - 1) / tqq, ta2 = (M + tqq - 1) / tqq;
+    const int ta1 = (N + kTileQ - 1) / kTileQ, ta2 = (M + kTileQ - 1) / kTileQ;
     const long long ablocks = (long long)B * (ta1 + ta2);
     const int aper = (int)((ablocks + 7) / 8);
-    // persistent: as many workgroups as stay resident (CUs x workgroups per CU by the image's size), a multiple of
-    // eight, at most one per tile; each walks the tiles w, w + grid, ... with the next tile's front loads in flight
-    static std::atomic<int> cus{0};
-    int ncu = cus.load(std::memory_order_relaxed);
-    if (ncu == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          ncu <= 0) {
-        (void)hipGetLastError();  // (tolerated: the chip's count)
-        ncu = 256;
-      }
-      cus.store(ncu, std::memory_order_relaxed);
-    }
-#define PP_LAUNCH_A(TQ_, CAP_, PER_CU_, WPE_)                                                                          \
-  do {                                                                                                          \
-    long long g_ = (long long)ncu * (PER_CU_);                                                                  \
-    g_ = (g_ < (long long)aper * 8 ? g_ : (long long)aper * 8);                                                 \
-    g_ = (g_ + 7) / 8 * 8;                                                                                      \
-    if ((PER_CU_) >= 1024) g_ += (2 * B + 7) / 8 * 8;  /* a workgroup per direction in front of the tiles': routing test, row bitmap */ \
-    if (own) {                                                                                                  \
-      hipExtLaunchKernelGGL((grid_stage_a_kernel<TQ_, CAP_, WPE_, ((PER_CU_) < 1024)>), dim3((unsigned)g_), dim3(TQ_), 0, s, \
-                            g_evk[2], g_evk[3], 0, dist1, idx1, dist2, idx2, ws, B, N, M, ta1, ta2, (int)ablocks, aper, lay, \
-                            route_dev, epoch, pre_routed);                                                        \
-      std::lock_guard<std::mutex> lock(g_ev_mutex);                                                              \
-      g_evk_valid = true;                                                                                        \
-    } else                                                                                                       \
-      grid_stage_a_kernel<TQ_, CAP_, WPE_, ((PER_CU_) < 1024)><<<dim3((unsigned)g_), dim3(TQ_), 0, s>>>(dist1, idx1, dist2, idx2, ws, B, N, M, ta1, \
-                                                                           ta2, (int)ablocks, aper, lay, route_dev, epoch, pre_routed); \
-  } while (0)
-    switch (tq) {
-      // (workgroups per CU: 1 << 20 = a workgroup per tile, not persistent -- measured as fast at config 2 (the front of
-      //  a tile is hidden by the other workgroups of the CU either way) and free of the loop's register pressure;
-      //  513: the persistent form, two workgroups per CU at 96 registers, kept for comparison)
-      case 256: PP_LAUNCH_A(256, 2044, 1 << 20, 4); break;
-      case 1024: PP_LAUNCH_A(1024, 4032, 1 << 20, 8); break;
-      case 513: PP_LAUNCH_A(512, 3068, 2, 5); break;
-      default: PP_LAUNCH_A(512, 3260, 1 << 20, 6); break;
-    }
-#undef PP_LAUNCH_A
+    // a workgroup per tile (a multiple of eight of them), behind a workgroup per direction in front of the tiles':
+    // routing test, row bitmap.  (a persistent form -- two workgroups per CU walking the tiles, each tile's front
+    // loads in flight during the tile before -- measured as fast at config 2, no faster: the front of a tile is hidden
+    // by the other workgroups of the CU either way, and the loop cost registers)
+    const unsigned agrid = (unsigned)((long long)aper * 8 + (2 * B + 7) / 8 * 8);
+    if (own) {
+      hipExtLaunchKernelGGL(grid_stage_a_kernel, dim3(agrid), dim3(kTileQ), 0, s, g_evk[2], g_evk[3], 0, dist1, idx1, dist2,
+                            idx2, ws, B, N, M, ta1, ta2, (int)ablocks, aper, lay, route_dev, epoch, pre_routed);
+      std::lock_guard<std::mutex> lock(g_ev_mutex);
+      g_evk_valid = true;
+    } else
+      grid_stage_a_kernel<<<dim3(agrid), dim3(kTileQ), 0, s>>>(dist1, idx1, dist2, idx2, ws, B, N, M, ta1, ta2, (int)ablocks,
+                                                              aper, lay, route_dev, epoch, pre_routed);
     PP_RETURN_IF_LAUNCH_FAILED();
     if (timing) record_timing_event(2, s);
   }
-#define PP_LAUNCH_W(CAP_)                                                                                  \
-  grid_query_wave_kernel<LAB, CAP_><<<dim3((unsigned)(per_xcd * 8)), dim3(256), 0, s>>>(                       \
-      xyz1, xyz2, dist1, idx1, dist2, idx2, ws, B, N, M, tiles1, tiles2, (int)blocks, per_xcd, label1, label2)
   if (two_stage) {
     // what stage A left: a wave for every 64 queries of a direction (as many as the whole-search kernel has, for the
     // clouds stage A cannot serve), every wave by itself
     const int sets = 2 * B;
     const int wps = ((N > M ? N : M) + 63) / 64;  // a wave for every 64 queries of a direction: as the whole-search kernel
     const long long lwaves = (long long)sets * wps;
-    // (the row bitmaps are written by the tail workgroups of the stage-A launch: the non-persistent forms)
-    const unsigned* rowbits = (tile != 513 && g_rowbits_mode != 1) ? reinterpret_cast<const unsigned*>(ws + lay.rowbits) : nullptr;
-    grid_query_list_kernel<384><<<dim3((unsigned)(((lwaves + kListWgWaves - 1) / kListWgWaves + 7) / 8 * 8)), dim3(64 * kListWgWaves), 0, s>>>(xyz1, xyz2, dist1, idx1, dist2, idx2,
+    // (the row bitmaps are written by the per-direction workgroups of the stage-A launch)
+    const unsigned* rowbits = g_rowbits_mode != 1 ? reinterpret_cast<const unsigned*>(ws + lay.rowbits) : nullptr;
+    grid_query_list_kernel<<<dim3((unsigned)(((lwaves + kListWgWaves - 1) / kListWgWaves + 7) / 8 * 8)), dim3(64 * kListWgWaves), 0, s>>>(xyz1, xyz2, dist1, idx1, dist2, idx2,
                                                                                       ws, B, N, M, wps, lay, pre_routed, rowbits);
     if (routing) {
       PP_RETURN_IF_LAUNCH_FAILED();
@@ -3352,13 +3281,9 @@ static int grid_forward(const float* xyz1, const float* xyz2, const float* label
       if (rc != PP_OK) return rc;
     }
   } else {
-    switch (g_stage_cap) {
-      case 320: PP_LAUNCH_W(320); break;
-      case 512: PP_LAUNCH_W(512); break;
-      default: PP_LAUNCH_W(384); break;
-    }
+    grid_query_wave_kernel<LAB><<<dim3((unsigned)(per_xcd * 8)), dim3(256), 0, s>>>(
+        xyz1, xyz2, dist1, idx1, dist2, idx2, ws, B, N, M, tiles1, tiles2, (int)blocks, per_xcd, label1, label2);
   }
-#undef PP_LAUNCH_W
   PP_RETURN_IF_LAUNCH_FAILED();
   if (timing) record_timing_event(3, s, two_stage);
   return PP_OK;

@@ -92,8 +92,7 @@ def _pair(fam, var, n, seed):
 # ------------------------------------------------------------------------------------------------ Chamfer fp32
 CHAMFER_PATHS = [{}, {"nmdistance_search": 1}, {"nmdistance_search": 2},
                  {"nmdistance_search": 2, "nmdistance_routing": 1}, {"nmdistance_search": 2, "nmdistance_routing": 2},
-                 {"nmdistance_search": 2, "nmdistance_build": 1}, {"nmdistance_search": 2, "nmdistance_tile": -1},
-                 {"nmdistance_search": 2, "nmdistance_tile": 512}] + \
+                 {"nmdistance_search": 2, "nmdistance_build": 1}, {"nmdistance_search": 2, "nmdistance_tile": -1}] + \
                 [{"nmdistance_search": 1, "nmdistance_variant": v} for v in (1, 416, 1008, 2004, 3004)]
 
 

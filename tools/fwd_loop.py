@@ -1,4 +1,4 @@
-"""python tools/fwd_loop.py TILE_MODE (pp_debug_set_nmdistance_tile) [kind] [iters]: nndistance forward at config 2 in a loop (for rocprofv3)"""
+"""python tools/fwd_loop.py TILE_MODE (pp_debug_set_nmdistance_tile: 0 or -1) [kind] [iters]: nndistance forward at config 2 in a loop (for rocprofv3)"""
 import ctypes, sys, numpy as np, torch
 sys.path.insert(0, ".")
 from pytorch_points_amd import _lib, synthetic as S

@@ -1,7 +1,7 @@
 """Phase clocks of grid_query_wave_kernel (p0 rows, p1 region, p2 copy, p3 stage A, p4 second level, p5 lane cubes,
 p6 whole-wave cubes, p7 group search, p8 the rest) (a -DPP_QUERY_PROBE build of the library,
 tools/libpp_hip_probe.so; the shipped library carries no stamps).  python tools/query_probe.py [tile mode ...]
-(modes: pp_debug_set_nmdistance_tile: -1 wave-private form, 256 / 512 / 768 queries per tile)"""
+(modes: pp_debug_set_nmdistance_tile: -1 wave-private form, 0 stage A by tiles then the list kernel)"""
 import ctypes, os, subprocess, sys, numpy as np, torch
 sys.path.insert(0, ".")
 from pytorch_points_amd import _build

@@ -1,5 +1,5 @@
 """forward time of nndistance at config-2 size on several point distributions, for the forms of the search kernel
-(pp_debug_set_nmdistance_tile: -1 the wave-private form of round 2, 256 / 512 / 768 queries per tile); every form is
+(pp_debug_set_nmdistance_tile: -1 the wave-private form of round 2, 0 stage A by tiles then the list kernel); every form is
 compared bit for bit with the every-pair kernel.  python tools/tile_modes.py [kinds...]"""
 import ctypes, sys, numpy as np, torch
 sys.path.insert(0, ".")
@@ -51,7 +51,7 @@ def clouds(kind, seed):
         if seed: x += 5.0
         return x
 kinds = sys.argv[1:] or ["sphere", "cube", "gaussian", "blobs8", "two_scales", "plane", "line", "shapenet_like", "disjoint"]
-modes = tuple(int(v) for v in os.environ.get("PP_TILE_MODES", "-1,512,513,1024").split(","))
+modes = tuple(int(v) for v in os.environ.get("PP_TILE_MODES", "-1,0").split(","))
 for kind in kinds:
     x1 = torch.from_numpy(np.ascontiguousarray(clouds(kind, 0))).to(dev); x2 = torch.from_numpy(np.ascontiguousarray(clouds(kind, 1))).to(dev)
     def outs():
