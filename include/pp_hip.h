@@ -349,6 +349,35 @@ int pp_gc3d_backward_f64(const double* query, const double* vertices, const long
                          const double* grad_gc_face, double* grad_query, double* grad_normals, int B, int P, int N,
                          int F, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- k-NN edge operators -------------------------------------------------------------------
+ * The (B,N,K,D) gather of a cloud's k-NN neighbourhoods and what the reference's point-cloud regularisers compute
+ * from it, without the gather; contract in DESIGN.md "k-NN edge operators".  points (B,N,D) fp32, idx int64 (B,N,K) as
+ * knn_points returns it, 1 <= K <= 128, 1 <= D <= 32 (D == 3 is specialised), N*K < 2^31.
+ * Edge lengths replace the gather + torch.norm of network/model_loss.py:120-127,147-152 and the gather + squared sum of
+ *   :378-385: out (B,N,K) = |points[idx[n,k]] - points[n]|^2 (the library's distance chain: bit-identical to
+ *   knn_points' dists), or its correctly rounded root when squared == 0.
+ * The Laplacian replaces network/geo_operations.py:128-152 pointUniformLaplacian:
+ *   lap (B,N,D) = -(sum_k points[idx[n,k]]) / K + points[n], the sum in ascending k.
+ * Backwards: gathers over the reverse adjacency of idx, built in a workspace of pp_knn_edges_workspace_bytes(B,N,K)
+ * bytes (not needed with detach_neighbors); grad_points (B,N,D) is overwritten.  `out` is the forward's output.
+ * detach_neighbors != 0: only the centre point of an edge receives its gradient (:379 detaches the neighbours).
+ * No floating-point atomics.  ordered != 0: every point adds its own edges in ascending k, then its incoming edges in
+ * ascending (n,k): reproducible bit for bit and equal to a sequential loop in that order; ordered == 0 leaves the
+ * order of the incoming terms unspecified.
+ * An index outside [0,N) is never dereferenced: that edge's length and that row of the Laplacian are NaN, and in the
+ * backwards the row takes no part in the scatter and its centre point's gradient is NaN. */
+size_t pp_knn_edges_workspace_bytes(int B, int N, int K);
+int pp_knn_edge_lengths_forward_f32(const float* points, const long long* idx, float* out, int B, int N, int K, int D,
+                                    int squared, void* stream);
+int pp_knn_edge_lengths_backward_f32(const float* points, const long long* idx, const float* out,
+                                     const float* grad_out, float* grad_points, int B, int N, int K, int D,
+                                     int squared, int detach_neighbors, int ordered, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int pp_knn_laplacian_forward_f32(const float* points, const long long* idx, float* lap, int B, int N, int K, int D,
+                                 void* stream);
+int pp_knn_laplacian_backward_f32(const long long* idx, const float* grad_lap, float* grad_points, int B, int N, int K,
+                                  int D, int ordered, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -1,11 +1,13 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
 furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
 (:88-126), the cage coordinates mean_value_coordinates_3D (:349-456) and green_coordinates_3D (:625-773), and the
-face normals those need, compute_face_normals_and_areas (:529-559).  The other mesh-geometry functions of that file
-are out of scope."""
+face normals those need, compute_face_normals_and_areas (:529-559), and the point-cloud Laplacian
+pointUniformLaplacian (:128-152).  The other mesh-geometry functions of that file are out of scope (SURVEY.md §2.1,
+DESIGN.md §7)."""
 import torch
 
 from .. import green as _green
+from .. import knn_edges as _knn_edges
 from .. import mvc as _mvc
 from .. import ops
 from .._ext import sampling
@@ -126,3 +128,14 @@ def green_coordinates_3D(query, vertices, faces, face_normals=None, verbose=Fals
     run fused HIP kernels; other devices and dtypes a torch composition of the same contract
     (pytorch_points_amd.green, DESIGN.md "Green coordinates")."""
     return _green.green_coordinates_3D(query, vertices, faces, face_normals, verbose)
+
+
+def pointUniformLaplacian(points, knn_idx=None, nn_size=3):
+    """Uniform Laplacian of a point cloud: ``(lap (B,N,D), knn_idx (B,N,K))`` with ``lap[n] = -mean_k points[knn_idx[n,k]]
+    + points[n]``.  ``knn_idx`` None: the ``nn_size`` nearest neighbours of every point (a search for ``nn_size + 1``
+    whose first column, the point itself, is dropped; reference :128-152).  No (B,N,K,D) gather is made
+    (pytorch_points_amd.knn_edges, DESIGN.md "k-NN edge operators")."""
+    if knn_idx is None:
+        assert(nn_size < points.shape[1])
+        knn_idx = ops.knn_points(points, points, K=nn_size + 1).idx[:, :, 1:]
+    return _knn_edges.knn_laplacian(points, knn_idx), knn_idx

@@ -1,6 +1,8 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.model_loss``: NmDistanceFunction /
-nndistance and LabeledNmdistanceFunction / labeled_nndistance (reference network/model_loss.py:401-483).
-The twelve torch-composed loss modules of that file are out of scope.
+nndistance and LabeledNmdistanceFunction / labeled_nndistance (reference network/model_loss.py:401-483), and the
+point-cloud regularisers PointLaplacianLoss, PointEdgeLengthLoss, PointStretchLoss, SmapeLoss, NormalLoss and
+SimplePointRepulsionLoss (:73-163, :310-398) over pytorch_points_amd.knn_edges.  The mesh losses of that file are out
+of scope.
 
 ``nndistance`` / ``labeled_nndistance`` are the C++ autograd nodes of csrc/torch_bridge.cpp (the reference's
 host side is a C++ extension too): at config 2 the step's kernels take less time than Python needs to issue
@@ -10,6 +12,8 @@ names; ``NmDistanceFunction.apply`` works as in the reference) and are tested to
 import torch
 
 from .. import _lib
+from .. import knn_edges as _knn_edges
+from .. import ops
 from .._ext import losses
 
 
@@ -124,3 +128,152 @@ def labeled_nndistance(xyz1, xyz2, label1, label2):
     """``labeled_nndistance(xyz1, xyz2, label1 (B,N), label2 (B,M))`` (reference :483), through the native
     autograd node."""
     return _lib.bridge().labeled_nndistance(xyz1, xyz2, label1, label2)
+
+
+# ------------------------------------------------------------------------------------- point-cloud regularisers
+# The reference's modules with its constructor and forward signatures, reductions and constants.  Graphs come from
+# ops.knn_points (a search for nn_size + 1 whose first column, the point itself, is dropped); edges and Laplacians
+# from pytorch_points_amd.knn_edges, which never makes the (B,N,K,D) gather.  INTEGRATION.md lists the three places
+# where the reference's text cannot run and what is done instead.
+def _self_graph(points, nn_size):
+    assert(nn_size < points.shape[1])
+    return ops.knn_points(points, points, K=nn_size + 1).idx[:, :, 1:]
+
+
+class PointLaplacianLoss(torch.nn.Module):
+    """``metric`` between the uniform Laplacians of two clouds in correspondence (reference :73-101): ``point2`` uses
+    the connectivity of ``point1``, or, with ``idx12`` (B,N), is gathered by it and searched on its own."""
+
+    def __init__(self, nn_size, metric, use_norm=False):
+        super().__init__()
+        self.metric = metric
+        self.nn_size = nn_size
+        self.use_norm = use_norm
+
+    def forward(self, point1, point2, idx12=None, *args, **kwargs):
+        from . import geo_operations as geo_op
+        lap1, knn_idx = geo_op.pointUniformLaplacian(point1, nn_size=self.nn_size)
+        if idx12 is not None:
+            point2 = torch.gather(point2, 1, idx12.unsqueeze(-1).expand(-1, -1, point2.shape[-1]))
+            lap2, _ = geo_op.pointUniformLaplacian(point2, nn_size=self.nn_size)
+        else:
+            assert(point2.shape[1] == point1.shape[1])
+            lap2, _ = geo_op.pointUniformLaplacian(point2, knn_idx=knn_idx)
+        if self.use_norm:
+            lap1 = torch.norm(lap1, dim=-1, p=2)
+            lap2 = torch.norm(lap2, dim=-1, p=2)
+        return self.metric(lap1, lap2)
+
+
+class PointEdgeLengthLoss(torch.nn.Module):
+    """``metric`` between the k-NN edge lengths of ``points_ref`` and the lengths of the same edges in ``points``
+    (reference :104-129)."""
+
+    def __init__(self, nn_size, metric):
+        super().__init__()
+        self.metric = metric
+        self.nn_size = nn_size
+
+    def forward(self, points_ref, points):
+        knn_idx = _self_graph(points_ref, self.nn_size)
+        dist_ref = _knn_edges.knn_edge_lengths(points_ref, knn_idx)
+        dist = _knn_edges.knn_edge_lengths(points, knn_idx)
+        return self.metric(dist_ref, dist)
+
+
+class PointStretchLoss(torch.nn.Module):
+    """Stretch only: ``max(d / (d_ref + 1e-10) - 1, 0)`` over the k-NN edges of ``points_ref`` (reference :132-163)."""
+
+    def __init__(self, nn_size, reduction="mean"):
+        super().__init__()
+        self.nn_size = nn_size
+        self.reduction = reduction
+
+    def forward(self, points_ref, points):
+        knn_idx = _self_graph(points_ref, self.nn_size)
+        dist_ref = _knn_edges.knn_edge_lengths(points_ref, knn_idx)
+        dist = _knn_edges.knn_edge_lengths(points, knn_idx)
+        stretch = torch.max(dist / (dist_ref + 1e-10) - 1, torch.zeros_like(dist))
+        if self.reduction == "mean":
+            return torch.mean(stretch)
+        elif self.reduction == "sum":
+            return torch.mean(torch.sum(stretch, dim=-1))
+        elif self.reduction == "none":
+            return stretch
+        elif self.reduction == "max":
+            return torch.mean(torch.max(stretch, dim=-1)[0])
+        else:
+            raise NotImplementedError
+
+
+class SmapeLoss(torch.nn.Module):
+    """Relative L1 norm ``mean(|x - y| / (|x| + |y| + epsilon))`` (reference :310-324)."""
+
+    def __init__(self, epsilon=1e-8):
+        super(SmapeLoss, self).__init__()
+        self.epsilon = epsilon
+
+    def forward(self, x, y):
+        return torch.mean(torch.abs(x - y) / (torch.abs(x) + torch.abs(y) + self.epsilon))
+
+
+class NormalLoss(torch.nn.Module):
+    """``1 - cos`` between the PCA normals of ``gt`` and ``pred`` (B,N,3) in correspondence (reference :326-358):
+    ``pred`` uses the neighbourhoods of ``gt``, or, with ``idx12`` (B,N), is gathered by it and searched on its own.
+    ``reduction="mean"`` is ``loss.mean()`` (the reference's ``loss.mean(loss)`` cannot run)."""
+
+    def __init__(self, nn_size=10, reduction="mean"):
+        super().__init__()
+        self.nn_size = nn_size
+        self.reduction = reduction
+        self.cos = torch.nn.CosineSimilarity(dim=-1, eps=1e-08)
+
+    def forward(self, gt, pred, idx12=None):
+        from . import geo_operations as geo_op
+        gt_normals, idx = geo_op.batch_normals(gt, nn_size=self.nn_size, NCHW=False)
+        if idx12 is not None:
+            pred = torch.gather(pred, 1, idx12.unsqueeze(-1).expand(-1, -1, 3))
+            pred_normals, _ = geo_op.batch_normals(pred, nn_size=self.nn_size, NCHW=False)
+        else:
+            pred_normals, _ = geo_op.batch_normals(pred, nn_size=self.nn_size, NCHW=False, idx=idx)
+        loss = 1 - self.cos(pred_normals, gt_normals)
+        if self.reduction == "mean":
+            return loss.mean()
+        elif self.reduction == "max":
+            return (torch.max(loss, dim=-1)[0]).mean()
+        elif self.reduction == "sum":
+            return torch.sum(loss, dim=-1).mean()
+        elif self.reduction == "none":
+            return loss
+
+
+class SimplePointRepulsionLoss(torch.nn.Module):
+    """``1 / sqrt(d^2 + 1e-4)`` over the k-NN edges shorter than ``radius`` (reference :362-398).  Without ``knn_idx``
+    the graph is searched here and the neighbours are detached, as in the reference; a supplied ``knn_idx`` (B,N,K)
+    passes gradients to both ends.  ``reduction="sum"`` is ``torch.sum(loss, -1).mean()`` (the reference's
+    ``loss.mean(torch.sum(...))`` cannot run)."""
+
+    def __init__(self, nn_size, radius, reduction="mean"):
+        super().__init__()
+        self.nn_size = nn_size
+        self.reduction = reduction
+        self.radius2 = radius * radius
+
+    def forward(self, points, knn_idx=None):
+        if knn_idx is None:
+            knn_idx = _self_graph(points, self.nn_size)
+            distance2 = _knn_edges.knn_edge_lengths(points, knn_idx, squared=True, detach_neighbors=True)
+        else:
+            distance2 = _knn_edges.knn_edge_lengths(points, knn_idx, squared=True)
+        loss = 1 / torch.sqrt(distance2 + 1e-4)
+        loss = torch.where(distance2 < self.radius2, loss, torch.zeros_like(loss))
+        if self.reduction == "mean":
+            return loss.mean()
+        elif self.reduction == "max":
+            return torch.mean(torch.max(loss, dim=-1)[0])
+        elif self.reduction == "sum":
+            return torch.sum(loss, dim=-1).mean()
+        elif self.reduction == "none":
+            return loss
+        else:
+            raise NotImplementedError
