@@ -378,6 +378,41 @@ int pp_knn_laplacian_forward_f32(const float* points, const long long* idx, floa
 int pp_knn_laplacian_backward_f32(const long long* idx, const float* grad_lap, float* grad_points, int B, int N, int K,
                                   int D, int ordered, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh edge operators -------------------------------------------------------------------
+ * What the reference's mesh losses (network/model_loss.py:166-308) and edge utilities (geo_operations.py:562-600) stand
+ * on; contract in DESIGN.md "Mesh edge operators".  int64 indices, fp32 vertices (B,N,3).  The two builds run once per
+ * topology, the two step kernels per training step.
+ * pp_mesh_unique_edges replaces edge_vertex_indices (torch.unique over the sorted half-edges): faces (Bt,F,3) ->
+ *   edges (Bt,3F,2): rows [0,counts[b]) the unique unordered vertex pairs as (min,max), ascending lexicographically
+ *   (torch.unique's rows, bit for bit; a face with a repeated vertex keeps its (a,a) pair), every later row (-1,-1);
+ *   counts (Bt) int32; flags (Bt) int32, non-zero where a face names a vertex outside [0,n_vertices): such an index is
+ *   only compared, its half-edges are left out.  The result does not depend on the order atomics are served in.
+ * pp_mesh_edge_incidence: edges (Bt,Ecap,2) -- any list: repeated pairs, unsorted, self-edges -- and counts (Bt) ->
+ *   inc_start (Bt,n_vertices+1) int32 and inc_entries (Bt,2*Ecap) uint32: vertex v's slice
+ *   [inc_start[v],inc_start[v+1]) holds 2*e + side for every e < counts[b] with edges[e,side] == v, ascending.  An end
+ *   outside [0,n_vertices) is only compared, left out, and ORed into flags (Bt), which the caller has initialised.
+ * Workspace: pp_mesh_edges_workspace_bytes(Bt, n_vertices, items) bytes, items = 3F for the unique edges and 2*Ecap
+ *   for the incidence (host arithmetic; 0 for an empty problem).  PP_EINVAL where Bt*items or Bt*(n_vertices+1) exceeds
+ *   2^31 - 1, the index words in use.
+ * pp_mesh_edge_sqrlen_forward_f32: out (B,Ecap) = |v[b,edges[e,0]] - v[b,edges[e,1]]|^2 for e < counts, 0 behind; the
+ *   library's distance chain (bit-identical to pp_knn_edge_lengths_forward_f32's squared form for the same pair).
+ *   shared_topology != 0: edges, counts and the incidence have one batch element, read by every b.
+ * pp_mesh_edge_sqrlen_backward_f32: grad_vertices (B,N,3), overwritten: every vertex walks its incidence slice in
+ *   order with t = (2 grad_out[b,e]) * (v_a - v_b); side 0 adds t, side 1 subtracts it; plain fp32 sums from 0.
+ *   Identical on every run and bit for bit the loop `for e: grad[a] += t; grad[b] -= t`.  No floating-point atomics.
+ * An edge with an end outside [0,N) reads nothing there: NaN length, NaN added to the gradient of its other end. */
+size_t pp_mesh_edges_workspace_bytes(int Bt, int n_vertices, long long items);
+int pp_mesh_unique_edges(const long long* faces, long long* edges, int* counts, int* flags, int Bt, int F,
+                         int n_vertices, void* workspace, size_t workspace_bytes, void* stream);
+int pp_mesh_edge_incidence(const long long* edges, const int* counts, int* inc_start, unsigned* inc_entries,
+                           int* flags, int Bt, int Ecap, int n_vertices, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int pp_mesh_edge_sqrlen_forward_f32(const float* vertices, const long long* edges, const int* counts, float* out,
+                                    int B, int N, int Ecap, int shared_topology, void* stream);
+int pp_mesh_edge_sqrlen_backward_f32(const float* vertices, const long long* edges, const int* inc_start,
+                                     const unsigned* inc_entries, const float* grad_out, float* grad_vertices, int B,
+                                     int N, int Ecap, int shared_topology, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

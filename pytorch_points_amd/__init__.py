@@ -1,10 +1,12 @@
 """pytorch_points_amd -- MI355X (gfx950) implementation of the pytorch_points `_ext` hot path.
 
 Drop-in for the reference's operator API on that path only:
-    pytorch_points.network.model_loss.{nndistance, labeled_nndistance}
+    pytorch_points.network.model_loss.{nndistance, labeled_nndistance, the point-cloud regularisers,
+        MeshEdgeLengthLoss, MeshStretchLoss, SimpleMeshRepulsionLoss}
     pytorch_points.network.operations.{gather_points, ball_query, grouping_operation, QueryAndGroup, batch_svd}
     pytorch_points.network.geo_operations.{furthest_point_sample, batch_normals, mean_value_coordinates_3D,
-        green_coordinates_3D, compute_face_normals_and_areas}
+        green_coordinates_3D, compute_face_normals_and_areas, pointUniformLaplacian, edge_vertex_indices,
+        get_edge_lengths}
     pytorch_points.network.pointnet2_utils.{three_nn, three_interpolate, QueryAndGroup, GroupAll}
     pytorch_points._ext.{losses, sampling, linalg}
 mean_value_coordinates_3D and green_coordinates_3D also accept CPU tensors and other dtypes, through torch

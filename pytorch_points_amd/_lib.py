@@ -85,6 +85,11 @@ SIGNATURES = {
     "pp_knn_edge_lengths_backward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
     "pp_knn_laplacian_forward_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "pp_knn_laplacian_backward_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_mesh_edges_workspace_bytes": [_I, _I, ctypes.c_longlong],
+    "pp_mesh_unique_edges": [_P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_mesh_edge_incidence": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_mesh_edge_sqrlen_forward_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_mesh_edge_sqrlen_backward_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_bytes": _c_size_t,
              "pp_nmdistance_forward_workspace_bytes": _c_size_t,
@@ -92,7 +97,8 @@ _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_byte
              "pp_scatter_workspace_bytes": _c_size_t, "pp_ball_query_workspace_bytes": _c_size_t,
              "pp_three_nn_workspace_bytes": _c_size_t, "pp_knn_workspace_bytes": _c_size_t,
              "pp_shard_packed_bytes": _c_size_t, "pp_mvc3d_workspace_bytes": _c_size_t,
-             "pp_gc3d_workspace_bytes": _c_size_t, "pp_knn_edges_workspace_bytes": _c_size_t}
+             "pp_gc3d_workspace_bytes": _c_size_t, "pp_knn_edges_workspace_bytes": _c_size_t,
+             "pp_mesh_edges_workspace_bytes": _c_size_t}
 
 _lib = None
 

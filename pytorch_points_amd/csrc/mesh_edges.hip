@@ -1,0 +1,475 @@
+// mesh_edges.hip -- the edge operators under the reference's mesh losses (network/model_loss.py:166-308,
+// geo_operations.py:562-600): MeshEdgeLengthLoss, MeshStretchLoss and SimpleMeshRepulsionLoss all work on the squared
+// lengths of a triangle mesh's unique edges.  The reference finds those edges per batch element with torch.unique (a
+// host synchronisation each), gathers an (E,2,3) tensor per mesh, and scatters back with floating-point atomics.
+//
+// Here the topology is built ONCE and kept (a mesh's connectivity does not change between training steps):
+//   unique edges   faces (Bt,F,3) -> edges (Bt,3F,2): the unordered vertex pairs as (min,max), ascending
+//                  lexicographically, rows from count[b] on (-1,-1); row for row what torch.unique(dim=0) of the sorted
+//                  half-edges returns.  Half-edges are bucketed by their min-vertex (integer atomics, a scan per batch
+//                  element, a fill through integer cursors), every bucket is SORTED by max-vertex, the first entry of
+//                  every run of equal pairs is ranked by a second scan and written compacted.  The sort makes the
+//                  result independent of the order in which the atomics were served.
+//   incidence      edges (Bt,Ecap,2), counts -> for every vertex the list of 2*e + side over the edges e < count[b]
+//                  with edges[e,side] == v, ascending (the same bucket / scan / fill / sort chain).  The edge list may
+//                  be any list: not unique, not sorted, with self-edges.
+// and a training step is two launches:
+//   forward        out[b,e] = |v[b,edges[e,0]] - v[b,edges[e,1]]|^2 (pp::chamfer_d3: the bits of knn_edge_lengths'
+//                  squared form), one thread per edge; 0 for the padding rows
+//   backward       a GATHER, one thread per vertex: grad starts at 0 and walks the vertex's incidence list in order,
+//                  t_e = (2 g[b,e]) * (v_a - v_b), side 0 adds t_e, side 1 subtracts it.  Plain fp32 sums in ascending
+//                  (e, side): the bits of the sequential loop `for e: grad[a] += t_e; grad[b] -= t_e`, on every run.
+//                  No floating-point atomics; there is no second form.
+// A topology with one batch element is shared by a batch of vertex sets (topology batch stride 0).
+//
+// An index outside [0, n_vertices) is never used as an address: the builds only compare it, skip what it belongs to and
+// set the batch element's flag word (the host raises); the forward writes NaN for such an edge and the backward adds NaN.
+#include "pp_common.h"
+
+namespace {
+
+constexpr int kMeThreads = 256;
+constexpr int kMeLongList = 256;    // buckets beyond this are sorted by a whole workgroup
+constexpr int kMeSortThreads = 1024;
+constexpr int kMeSortBlocks = 256;
+constexpr int kMeScanThreads = 1024;
+
+// scratch of one build: `items` entries per batch element (3F half-edges, or 2*Ecap edge ends) over N vertices
+struct MeLayout {
+  size_t nlong, cursor, start, longlist, entries, owner, total;
+};
+__host__ __device__ inline size_t me_align(size_t x) { return (x + 255) & ~(size_t)255; }
+__host__ __device__ inline MeLayout me_layout(int Bt, int N, long long items) {
+  const size_t rows = (size_t)Bt * N, all = (size_t)Bt * (size_t)items;
+  MeLayout L;
+  L.nlong = 0;                                 // one counter; zeroed together with the cursors behind it
+  L.cursor = 256;                              // u32 [Bt*N]: bucket size, then fill cursor, finally the bucket's end
+  L.start = L.cursor + me_align(4 * rows);     // u32 [Bt*N]: the bucket's first entry (within the batch element)
+  L.longlist = L.start + me_align(4 * rows);   // u32 [all / kMeLongList + 1]: buckets with a long list
+  L.entries = L.longlist + me_align(4 * (all / kMeLongList + 1));
+  L.owner = L.entries + me_align(4 * all);     // u32 [Bt][items]: the bucket of every entry (unique edges only)
+  L.total = L.owner + me_align(4 * all);
+  return L;
+}
+
+__device__ __forceinline__ float me_nan() { return __int_as_float(0x7fc00000); }
+
+// ---- buckets ------------------------------------------------------------------------------------------------------
+// Half-edge j of face f joins corners j and (j+1) mod 3.  FILL = false: bucket sizes by min-vertex; FILL = true: the
+// buckets receive the max-vertices (and every position its bucket).  A half-edge with an index outside [0, N) is only
+// compared: it sets its batch element's flag and takes no part.
+template <bool FILL>
+__global__ __launch_bounds__(kMeThreads) void me_half_edges_kernel(const long long* __restrict__ faces,
+                                                                   unsigned* __restrict__ cursor,
+                                                                   unsigned* __restrict__ entries,
+                                                                   unsigned* __restrict__ owner,
+                                                                   int* __restrict__ flags, long long total, int F,
+                                                                   int N) {
+  const long long h = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (h >= total) return;
+  const long long H = 3LL * F;
+  const long long b = h / H;
+  const long long f = h / 3;          // face number over the whole batch
+  const int j = (int)(h - f * 3);
+  const long long p = faces[f * 3 + j], q = faces[f * 3 + (j == 2 ? 0 : j + 1)];
+  if (p < 0 || p >= N || q < 0 || q >= N) {
+    if (!FILL) atomicOr(flags + b, 1);
+    return;
+  }
+  const unsigned mn = (unsigned)(p < q ? p : q), mx = (unsigned)(p < q ? q : p);
+  unsigned* cur = cursor + (size_t)b * N + mn;
+  if (!FILL) {
+    atomicAdd(cur, 1u);
+  } else {
+    const unsigned pos = atomicAdd(cur, 1u);   // < 3F: a batch element has no more valid half-edges than that
+    entries[(size_t)b * H + pos] = mx;
+    owner[(size_t)b * H + pos] = mn;
+  }
+}
+
+// One thread per edge end (b, e, side), e < counts[b].  FILL = false: the vertices' degrees; FILL = true: the lists
+// receive 2*e + side.  An end outside [0, N) sets the flag and takes no part.
+template <bool FILL>
+__global__ __launch_bounds__(kMeThreads) void me_edge_ends_kernel(const long long* __restrict__ edges,
+                                                                  const int* __restrict__ counts,
+                                                                  unsigned* __restrict__ cursor,
+                                                                  unsigned* __restrict__ entries,
+                                                                  int* __restrict__ flags, long long total, int Ecap,
+                                                                  int N) {
+  const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long X = 2LL * Ecap;
+  const long long b = x / X;
+  const unsigned code = (unsigned)(x - b * X);   // 2*e + side
+  if ((int)(code >> 1) >= counts[b]) return;
+  const long long v = edges[x];
+  if (v < 0 || v >= N) {
+    if (!FILL) atomicOr(flags + b, 1);
+    return;
+  }
+  unsigned* cur = cursor + (size_t)b * N + (size_t)v;
+  if (!FILL) {
+    atomicAdd(cur, 1u);
+  } else {
+    const unsigned pos = atomicAdd(cur, 1u);   // < 2*Ecap
+    entries[(size_t)b * X + pos] = code;
+  }
+}
+
+// exclusive scan of one chunk of kMeScanThreads values inside a workgroup; returns the value's exclusive prefix
+// including `carry`, and leaves the chunk's total in *chunk_total (valid after the call for every thread)
+__device__ __forceinline__ unsigned me_block_scan(unsigned v, unsigned carry, unsigned* s_wave, unsigned* chunk_total) {
+  const int t = threadIdx.x;
+  unsigned incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned o = __shfl_up(incl, off);
+    if ((t & 63) >= off) incl += o;
+  }
+  __syncthreads();   // the previous chunk's readers of s_wave are done
+  if ((t & 63) == 63) s_wave[t >> 6] = incl;
+  __syncthreads();
+  unsigned run = carry + incl - v, all = 0;
+  for (int w = 0; w < kMeScanThreads / 64; ++w) {
+    const unsigned s = s_wave[w];
+    if (w < (t >> 6)) run += s;
+    all += s;
+  }
+  *chunk_total = all;
+  return run;
+}
+
+// one workgroup per batch element: exclusive scan of the bucket sizes -> start, cursor; start2 (nullable, stride N+1,
+// the incidence's public form) receives the same values and the total behind them
+__global__ __launch_bounds__(kMeScanThreads) void me_scan_kernel(unsigned* __restrict__ cursor,
+                                                                 unsigned* __restrict__ start,
+                                                                 int* __restrict__ start2, int N) {
+  __shared__ unsigned s_wave[kMeScanThreads / 64];
+  const int t = threadIdx.x;
+  unsigned* cur = cursor + (size_t)blockIdx.x * N;
+  unsigned* st = start + (size_t)blockIdx.x * N;
+  int* st2 = start2 ? start2 + (size_t)blockIdx.x * ((size_t)N + 1) : nullptr;
+  unsigned carry = 0;
+  for (int i0 = 0; i0 < N; i0 += kMeScanThreads) {
+    const int i = i0 + t;
+    const unsigned v = i < N ? cur[i] : 0u;
+    unsigned chunk;
+    const unsigned run = me_block_scan(v, carry, s_wave, &chunk);
+    if (i < N) {
+      st[i] = run;
+      cur[i] = run;
+      if (st2) st2[i] = (int)run;
+    }
+    carry += chunk;
+  }
+  if (st2 && t == 0) st2[N] = (int)carry;
+}
+
+// one lane per bucket sorts it ascending (pp::lane_sort); a bucket beyond kMeLongList entries is left to
+// me_sort_long_kernel.  Equal keys (a pair that several faces share) need no order among themselves.
+__global__ __launch_bounds__(kMeThreads) void me_sort_kernel(const unsigned* __restrict__ start,
+                                                             const unsigned* __restrict__ cursor,
+                                                             unsigned* __restrict__ entries,
+                                                             unsigned* __restrict__ nlong,
+                                                             unsigned* __restrict__ longlist, long long rows, int N,
+                                                             long long items) {
+  const long long i = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (i >= rows) return;
+  const unsigned s = start[i], n = cursor[i] - s;
+  if (n > (unsigned)kMeLongList) {
+    longlist[atomicAdd(nlong, 1u)] = (unsigned)i;   // rows < 2^31 is checked by the host; at most all/256 long buckets
+    return;
+  }
+  unsigned* grp = entries + (size_t)(i / N) * (size_t)items + s;
+  pp::lane_sort(
+      n, [&](unsigned a) { return grp[a]; },
+      [&](unsigned a, unsigned b) {
+        const unsigned e = grp[a];
+        grp[a] = grp[b];
+        grp[b] = e;
+      });
+}
+
+// a workgroup per long bucket: bitonic network in place with every comparison ascending (the first step of a merge
+// pairs i with its mirror image in the block), so that a list of any length sorts as if padded with +inf
+__global__ __launch_bounds__(kMeSortThreads) void me_sort_long_kernel(const unsigned* __restrict__ start,
+                                                                      const unsigned* __restrict__ cursor,
+                                                                      unsigned* entries, const unsigned* nlong,
+                                                                      const unsigned* longlist, int N,
+                                                                      long long items) {
+  const unsigned count = *nlong;
+  for (unsigned q = blockIdx.x; q < count; q += gridDim.x) {
+    const unsigned i = longlist[q];
+    const unsigned s = start[i], n = cursor[i] - s;
+    unsigned* grp = entries + (size_t)(i / (unsigned)N) * (size_t)items + s;
+    auto pass = [&](unsigned mask) {
+      for (unsigned a = threadIdx.x; a < n; a += kMeSortThreads) {
+        const unsigned b = a ^ mask;
+        if (b > a && b < n) {
+          const unsigned x = grp[a], y = grp[b];
+          if (x > y) {
+            grp[a] = y;
+            grp[b] = x;
+          }
+        }
+      }
+      __syncthreads();
+    };
+    for (unsigned k = 2; (k >> 1) < n; k <<= 1) {
+      pass(k - 1);
+      for (unsigned j = k >> 2; j > 0; j >>= 1) pass(j);
+    }
+  }
+}
+
+// one workgroup per batch element over its sorted (owner, entry) pairs: a position that differs from the one before it
+// starts a run; the runs are ranked by a scan and written compacted, then the rows behind them are padded with -1
+__global__ __launch_bounds__(kMeScanThreads) void me_compact_kernel(const unsigned* __restrict__ cursor,
+                                                                    const unsigned* __restrict__ entries,
+                                                                    const unsigned* __restrict__ owner,
+                                                                    long long* __restrict__ edges,
+                                                                    int* __restrict__ counts, int N, int F) {
+  __shared__ unsigned s_wave[kMeScanThreads / 64];
+  const int t = threadIdx.x;
+  const size_t H = 3 * (size_t)F;
+  const unsigned* __restrict__ ent = entries + (size_t)blockIdx.x * H;
+  const unsigned* __restrict__ own = owner + (size_t)blockIdx.x * H;
+  long long* __restrict__ out = edges + (size_t)blockIdx.x * H * 2;
+  const unsigned T = N > 0 ? cursor[(size_t)blockIdx.x * N + (N - 1)] : 0u;   // the last bucket's end: valid half-edges
+  unsigned carry = 0;
+  for (unsigned q0 = 0; q0 < T; q0 += kMeScanThreads) {
+    const unsigned q = q0 + t;
+    unsigned first = 0, mn = 0, mx = 0;
+    if (q < T) {
+      mn = own[q];
+      mx = ent[q];
+      first = (q == 0 || own[q - 1] != mn || ent[q - 1] != mx) ? 1u : 0u;
+    }
+    unsigned chunk;
+    const unsigned rank = me_block_scan(first, carry, s_wave, &chunk);
+    if (first) {
+      out[2 * (size_t)rank] = (long long)mn;
+      out[2 * (size_t)rank + 1] = (long long)mx;
+    }
+    carry += chunk;
+  }
+  if (t == 0) counts[blockIdx.x] = (int)carry;
+  for (size_t w = 2 * (size_t)carry + t; w < 2 * H; w += kMeScanThreads) out[w] = -1;
+}
+
+// ---- the step -----------------------------------------------------------------------------------------------------
+// one thread per edge
+__global__ __launch_bounds__(kMeThreads) void me_sqrlen_forward_kernel(const float* __restrict__ vertices,
+                                                                       const long long* __restrict__ edges,
+                                                                       const int* __restrict__ counts,
+                                                                       float* __restrict__ out, long long total, int N,
+                                                                       int Ecap, int shared) {
+  const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long b = x / Ecap;
+  const long long e = x - b * Ecap;
+  const long long tb = shared ? 0 : b;
+  if (e >= counts[tb]) {
+    out[x] = 0.0f;
+    return;
+  }
+  const long long a = edges[(tb * Ecap + e) * 2], c = edges[(tb * Ecap + e) * 2 + 1];
+  if (a < 0 || a >= N || c < 0 || c >= N) {
+    out[x] = me_nan();
+    return;
+  }
+  const float* __restrict__ pa = vertices + ((size_t)b * N + (size_t)a) * 3;
+  const float* __restrict__ pc = vertices + ((size_t)b * N + (size_t)c) * 3;
+  out[x] = pp::chamfer_d3(pa[0], pa[1], pa[2], pc[0], pc[1], pc[2]);
+}
+
+// one thread per vertex; the incidence list in order, however long it is
+__global__ __launch_bounds__(kMeThreads) void me_sqrlen_backward_kernel(
+    const float* __restrict__ vertices, const long long* __restrict__ edges, const int* __restrict__ inc_start,
+    const unsigned* __restrict__ inc_entries, const float* __restrict__ g, float* __restrict__ grad, long long rows,
+    int N, int Ecap, int shared) {
+  const long long i = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (i >= rows) return;
+  const long long b = i / N;
+  const long long v = i - b * N;
+  const long long tb = shared ? 0 : b;
+  const float* __restrict__ vb = vertices + (size_t)b * N * 3;
+  const long long* __restrict__ eb = edges + (size_t)tb * Ecap * 2;
+  const unsigned* __restrict__ list = inc_entries + (size_t)tb * Ecap * 2;
+  const float* __restrict__ gb = g + (size_t)b * Ecap;
+  const int* __restrict__ st = inc_start + (size_t)tb * ((size_t)N + 1) + v;
+  const float px = vb[v * 3], py = vb[v * 3 + 1], pz = vb[v * 3 + 2];
+  float ax = 0.0f, ay = 0.0f, az = 0.0f;
+  for (int q = st[0], q1 = st[1]; q < q1; ++q) {
+    const unsigned code = list[q];
+    const unsigned e = code >> 1, side = code & 1u;
+    const long long o = eb[2 * (size_t)e + (side ^ 1u)];   // the other end; this end is v
+    const float coef = 2.0f * gb[e];
+    float tx, ty, tz;
+    if (o < 0 || o >= N) {
+      tx = ty = tz = me_nan();
+    } else {
+      const float ox = vb[o * 3], oy = vb[o * 3 + 1], oz = vb[o * 3 + 2];
+      // v_a - v_b with a = edges[e,0], b = edges[e,1]
+      tx = coef * (side ? ox - px : px - ox);
+      ty = coef * (side ? oy - py : py - oy);
+      tz = coef * (side ? oz - pz : pz - oz);
+    }
+    if (side) {
+      ax = ax - tx;
+      ay = ay - ty;
+      az = az - tz;
+    } else {
+      ax = ax + tx;
+      ay = ay + ty;
+      az = az + tz;
+    }
+  }
+  grad[i * 3] = ax;
+  grad[i * 3 + 1] = ay;
+  grad[i * 3 + 2] = az;
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------
+// the index words in use: u32 positions and codes within a batch element, int32 starts, 31-bit grids
+bool me_build_ok(int Bt, int N, long long items) {
+  return Bt >= 0 && N >= 0 && items >= 0 && (long long)Bt * items <= 0x7fffffffLL && (long long)Bt * N <= 0x7fffffffLL;
+}
+
+unsigned me_blocks(long long work, int per_block) { return (unsigned)((work + per_block - 1) / per_block); }
+
+int me_sort_buckets(unsigned char* ws, const MeLayout& L, unsigned* entries, int Bt, int N, long long items,
+                    hipStream_t s) {
+  const long long rows = (long long)Bt * N;
+  unsigned* nlong = reinterpret_cast<unsigned*>(ws + L.nlong);
+  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
+  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
+  unsigned* longlist = reinterpret_cast<unsigned*>(ws + L.longlist);
+  me_sort_kernel<<<dim3(me_blocks(rows, kMeThreads)), dim3(kMeThreads), 0, s>>>(start, cursor, entries, nlong, longlist,
+                                                                                 rows, N, items);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_sort_long_kernel<<<dim3(kMeSortBlocks), dim3(kMeSortThreads), 0, s>>>(start, cursor, entries, nlong, longlist, N,
+                                                                           items);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t pp_mesh_edges_workspace_bytes(int Bt, int n_vertices, long long items) {
+  if (Bt <= 0 || n_vertices <= 0 || items <= 0 || !me_build_ok(Bt, n_vertices, items)) return 0;
+  return me_layout(Bt, n_vertices, items).total;
+}
+
+extern "C" int pp_mesh_unique_edges(const long long* faces, long long* edges, int* counts, int* flags, int Bt, int F,
+                                    int n_vertices, void* workspace, size_t workspace_bytes, void* stream) {
+  const long long H = 3LL * (F > 0 ? F : 0);
+  const int N = n_vertices;
+  if (F < 0 || !me_build_ok(Bt, N, H)) return PP_EINVAL;
+  if (Bt == 0) return PP_OK;
+  if (!counts || !flags) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = pp::fill_bytes(flags, 0, 4 * (size_t)Bt, s);
+  if (e != hipSuccess) return (int)e;
+  if (F == 0 || N == 0) {   // no face, or no vertex a face could name: no edges (a face of an empty mesh is flagged)
+    e = pp::fill_bytes(counts, 0, 4 * (size_t)Bt, s);
+    if (e != hipSuccess) return (int)e;
+    if (F == 0) return PP_OK;
+    if (!edges) return PP_EINVAL;
+    e = pp::fill_bytes(edges, 0xff, (size_t)Bt * H * 16, s);
+    if (e != hipSuccess) return (int)e;
+    return (int)pp::fill_bytes(flags, 1, 4 * (size_t)Bt, s);   // (any non-zero word)
+  }
+  const MeLayout L = me_layout(Bt, N, H);
+  unsigned char* ws = (unsigned char*)workspace;
+  if (!faces || !edges || !ws || workspace_bytes < L.total) return PP_EINVAL;
+  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
+  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
+  unsigned* entries = reinterpret_cast<unsigned*>(ws + L.entries);
+  unsigned* owner = reinterpret_cast<unsigned*>(ws + L.owner);
+  e = pp::fill_bytes(ws, 0, L.start, s);   // the counter and the bucket sizes
+  if (e != hipSuccess) return (int)e;
+  const long long total = (long long)Bt * H;
+  me_half_edges_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, entries,
+                                                                                               owner, flags, total, F, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_scan_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, start, nullptr, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_half_edges_kernel<true><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, entries,
+                                                                                              owner, flags, total, F, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  const int rc = me_sort_buckets(ws, L, entries, Bt, N, H, s);
+  if (rc != PP_OK) return rc;
+  me_compact_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, entries, owner, edges, counts, N, F);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_edge_incidence(const long long* edges, const int* counts, int* inc_start, unsigned* inc_entries,
+                                      int* flags, int Bt, int Ecap, int n_vertices, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  const long long X = 2LL * (Ecap > 0 ? Ecap : 0);
+  const int N = n_vertices;
+  if (Ecap < 0 || !me_build_ok(Bt, N, X) || (long long)Bt * ((long long)N + 1) > 0x7fffffffLL) return PP_EINVAL;
+  if (Bt == 0) return PP_OK;
+  if (!inc_start) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (Ecap == 0 || N == 0) {   // no list has an entry
+    const hipError_t e = pp::fill_bytes(inc_start, 0, 4 * (size_t)Bt * ((size_t)N + 1), s);
+    if (e != hipSuccess) return (int)e;
+    if (Ecap == 0) return PP_OK;
+  }
+  if (!edges || !counts || !flags) return PP_EINVAL;
+  const long long total = (long long)Bt * X;
+  if (N == 0) {   // every end of every counted edge is out of range: the count pass only compares and flags
+    me_edge_ends_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(
+        edges, counts, nullptr, nullptr, flags, total, Ecap, N);
+    PP_RETURN_IF_LAUNCH_FAILED();
+    return PP_OK;
+  }
+  const MeLayout L = me_layout(Bt, N, X);
+  unsigned char* ws = (unsigned char*)workspace;
+  if (!inc_entries || !ws || workspace_bytes < L.entries) return PP_EINVAL;   // the lists are built in place
+  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
+  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
+  unsigned* entries = inc_entries;
+  hipError_t e = pp::fill_bytes(ws, 0, L.start, s);
+  if (e != hipSuccess) return (int)e;
+  me_edge_ends_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(edges, counts, cursor,
+                                                                                              entries, flags, total, Ecap, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_scan_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, start, inc_start, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_edge_ends_kernel<true><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(edges, counts, cursor,
+                                                                                             entries, flags, total, Ecap, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return me_sort_buckets(ws, L, entries, Bt, N, X, s);
+}
+
+extern "C" int pp_mesh_edge_sqrlen_forward_f32(const float* vertices, const long long* edges, const int* counts,
+                                               float* out, int B, int N, int Ecap, int shared_topology, void* stream) {
+  if (B < 0 || N < 0 || Ecap < 0 || (long long)B * Ecap > 0x7fffffffLL * (long long)kMeThreads ||
+      (long long)B * N > 0x7fffffffLL)
+    return PP_EINVAL;
+  if (B == 0 || Ecap == 0) return PP_OK;
+  if (!edges || !counts || !out || (N > 0 && !vertices)) return PP_EINVAL;
+  const long long total = (long long)B * Ecap;
+  me_sqrlen_forward_kernel<<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
+      vertices, edges, counts, out, total, N, Ecap, shared_topology != 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_edge_sqrlen_backward_f32(const float* vertices, const long long* edges, const int* inc_start,
+                                                const unsigned* inc_entries, const float* grad_out,
+                                                float* grad_vertices, int B, int N, int Ecap, int shared_topology,
+                                                void* stream) {
+  if (B < 0 || N < 0 || Ecap < 0 || (long long)B * N > 0x7fffffffLL || 2LL * Ecap > 0x7fffffffLL) return PP_EINVAL;
+  if (B == 0 || N == 0) return PP_OK;
+  if (!vertices || !inc_start || !grad_vertices || (Ecap > 0 && (!edges || !inc_entries || !grad_out))) return PP_EINVAL;
+  const long long rows = (long long)B * N;
+  me_sqrlen_backward_kernel<<<dim3(me_blocks(rows, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
+      vertices, edges, inc_start, inc_entries, grad_out, grad_vertices, rows, N, Ecap, shared_topology != 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}

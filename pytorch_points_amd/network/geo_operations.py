@@ -1,13 +1,15 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
 furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
 (:88-126), the cage coordinates mean_value_coordinates_3D (:349-456) and green_coordinates_3D (:625-773), and the
-face normals those need, compute_face_normals_and_areas (:529-559), and the point-cloud Laplacian
-pointUniformLaplacian (:128-152).  The other mesh-geometry functions of that file are out of scope (SURVEY.md §2.1,
-DESIGN.md §7)."""
+face normals those need, compute_face_normals_and_areas (:529-559), the point-cloud Laplacian
+pointUniformLaplacian (:128-152), and the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600).
+The other mesh-geometry functions of that file are out of scope."""
+import numpy as np
 import torch
 
 from .. import green as _green
 from .. import knn_edges as _knn_edges
+from .. import mesh_edges as _mesh_edges
 from .. import mvc as _mvc
 from .. import ops
 from .._ext import sampling
@@ -139,3 +141,49 @@ def pointUniformLaplacian(points, knn_idx=None, nn_size=3):
         assert(nn_size < points.shape[1])
         knn_idx = ops.knn_points(points, points, K=nn_size + 1).idx[:, :, 1:]
     return _knn_edges.knn_laplacian(points, knn_idx), knn_idx
+
+
+def edge_vertex_indices(F):
+    """Unique edges ``(E,2)`` of the triangle list ``F`` (F,3): every face's corner pairs as (min,max), the distinct
+    rows in ascending lexicographic order (reference :562-583).  A CUDA integer tensor runs the HIP build with
+    ``n_vertices = F.max() + 1`` and is sliced by the count it reports: two host reads (the reference's
+    ``torch.unique`` synchronises too); a negative index raises IndexError there.  A CPU tensor goes through the
+    torch composition, a numpy array through ``np.unique`` and comes back as numpy.  For a loop that keeps its
+    topology, build a ``pytorch_points_amd.mesh_edges.MeshEdges`` once instead."""
+    if not isinstance(F, torch.Tensor):
+        F = np.asarray(F)
+        pairs = np.sort(np.stack([F, F[:, [1, 2, 0]]], axis=-1), axis=-1)
+        return np.unique(pairs.reshape([-1, 2]), axis=0)
+    if F.dim() != 2 or F.shape[1] != 3:
+        raise NotImplementedError("edge_vertex_indices: F must have shape (F, 3) (triangles), got %s" % (tuple(F.shape),))
+    if not _mesh_edges._is_index(F):
+        raise TypeError("edge_vertex_indices: F must be an integer tensor, got %s" % F.dtype)
+    if not F.is_cuda or F.shape[0] == 0:
+        return _mesh_edges.unique_edges_composition(F)
+    fl = (F if F.dtype == torch.int64 else F.long()).contiguous().unsqueeze(0)
+    n_vertices = int(fl.max()) + 1                                        # host read 1
+    status = torch.empty(2, 1, dtype=torch.int32, device=F.device)
+    edges = _mesh_edges._unique_edges_hip(fl, max(n_vertices, 0), status)
+    count, flag = status[:, 0].tolist()                                   # host read 2
+    if flag:
+        raise IndexError("edge_vertex_indices: F holds a negative vertex index")
+    return edges[0, :count].to(F.dtype)
+
+
+def get_edge_lengths(vertices, edge_points):
+    """SQUARED lengths ``(E,)`` of the edges ``edge_points[:, :2]`` over ``vertices`` (N,D), despite the name
+    (reference :586-600).  CUDA fp32 with D = 3 runs the HIP kernel; its backward builds the edges' vertex incidence
+    when, and only when, a gradient is asked for.  Nothing synchronises with the host: on that path an index outside
+    [0, N) gives a NaN length (the reference wraps a negative index and faults on a large one)."""
+    if vertices.dim() != 2 or edge_points.dim() != 2 or edge_points.shape[1] < 2:
+        raise ValueError("get_edge_lengths: vertices (N, D) and edge_points (E, >= 2), got %s and %s"
+                         % (tuple(vertices.shape), tuple(edge_points.shape)))
+    if vertices.is_cuda and vertices.dtype == torch.float32 and vertices.shape[1] == 3 and edge_points.is_cuda:
+        if not _mesh_edges._is_index(edge_points):
+            raise TypeError("get_edge_lengths: edge_points must be an integer tensor, got %s" % edge_points.dtype)
+        edges = edge_points[:, :2].long().contiguous().unsqueeze(0)
+        topo = _mesh_edges.MeshEdges._unchecked(edges, vertices.shape[0])
+        return _mesh_edges.mesh_edge_sqrlen(vertices.unsqueeze(0), topo)[0]
+    ends = vertices[edge_points[:, :2]]
+    t = ends[:, 0, :] - ends[:, 1, :]
+    return torch.sum(t * t, dim=-1)

@@ -1,8 +1,9 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.model_loss``: NmDistanceFunction /
 nndistance and LabeledNmdistanceFunction / labeled_nndistance (reference network/model_loss.py:401-483), and the
 point-cloud regularisers PointLaplacianLoss, PointEdgeLengthLoss, PointStretchLoss, SmapeLoss, NormalLoss and
-SimplePointRepulsionLoss (:73-163, :310-398) over pytorch_points_amd.knn_edges.  The mesh losses of that file are out
-of scope.
+SimplePointRepulsionLoss (:73-163, :310-398) over pytorch_points_amd.knn_edges, and the mesh edge losses
+MeshEdgeLengthLoss, MeshStretchLoss and SimpleMeshRepulsionLoss (:166-308) over pytorch_points_amd.mesh_edges.  The
+Laplacian mesh losses of that file are out of scope.
 
 ``nndistance`` / ``labeled_nndistance`` are the C++ autograd nodes of csrc/torch_bridge.cpp (the reference's
 host side is a C++ extension too): at config 2 the step's kernels take less time than Python needs to issue
@@ -13,6 +14,7 @@ import torch
 
 from .. import _lib
 from .. import knn_edges as _knn_edges
+from .. import mesh_edges as _mesh_edges
 from .. import ops
 from .._ext import losses
 
@@ -277,3 +279,132 @@ class SimplePointRepulsionLoss(torch.nn.Module):
             return loss
         else:
             raise NotImplementedError
+
+
+# ------------------------------------------------------------------------------------------- mesh edge losses
+# The reference's modules (:166-308) with its constructor and forward signatures, reductions and constants.  All three
+# work on SQUARED edge lengths (geo_operations.get_edge_lengths returns squares).  The unique edges come from
+# pytorch_points_amd.mesh_edges.MeshEdges -- one build with one host read for the whole batch, where the reference
+# loops over the batch with a torch.unique each -- and the lengths of every batch element from one launch.
+def _get_ev(faces, n_vertices):
+    """a list of B ``(E_b,2)`` int64 tensors: the unique edges of every batch element of ``faces`` (B,F,3)"""
+    topo = _mesh_edges.MeshEdges.from_faces(faces, n_vertices)
+    return [topo.edge_list(b) for b in range(faces.shape[0])]
+
+
+def _edge_mask(topo, like):
+    """``(valid (Bt,Ecap) bool, count (Bt,1) in the dtype of ``like``)``, from the device counts: no host read"""
+    count = topo.counts[:, None]
+    valid = torch.arange(topo.capacity, device=like.device)[None, :] < count
+    return valid, count.to(like.dtype)
+
+
+def _reduce_edges(values, topo, reduction):
+    """The reference's per-element reduction of ``values`` (B,Ecap) over each element's own edges, then over the
+    batch, as batched operations: padding rows count as 0 and a mean divides by ``count[b]``."""
+    if reduction not in ("mean", "none", "max", "sum"):
+        raise NotImplementedError
+    valid, count = _edge_mask(topo, values)
+    values = torch.where(valid, values, torch.zeros_like(values))
+    if reduction == "max":
+        per = torch.max(values, dim=-1)[0]
+    elif reduction == "sum":
+        per = torch.sum(values, dim=-1)
+    else:
+        per = torch.sum(values, dim=-1) / count[:, 0]
+    return per if reduction == "none" else per.mean()
+
+
+class _MeshTopologyLoss(torch.nn.Module):
+    """the topology handling the two face-based losses share: ``self.E`` is the ``MeshEdges`` of the last build; it
+    is kept, and never checked against later faces, while ``consistent_topology`` is set (reference :195-197)"""
+
+    def __init__(self, consistent_topology):
+        super().__init__()
+        self.E = None
+        self.consistent_topology = consistent_topology
+
+    @staticmethod
+    def getEV(faces, n_vertices):
+        """return a list of B (E, 2) int64 tensor"""
+        return _get_ev(faces, n_vertices)
+
+    def _topology(self, vert1, vert2, face):
+        assert(vert1.shape == vert2.shape)
+        if (not self.consistent_topology) or (self.E is None):
+            assert(face is not None), "Face is required"
+            self.E = _mesh_edges.MeshEdges.from_faces(face, vert1.shape[1])
+        return self.E
+
+
+class MeshEdgeLengthLoss(_MeshTopologyLoss):
+    """Mean over the batch of ``metric(sq1[b], sq2[b])`` between the squared edge lengths of two meshes of one
+    topology, ``vert1`` and ``vert2`` (B,N,3) with ``face`` (B,F,3) (reference :166-209).  ``metric`` is any callable,
+    so it is called once per batch element on views of the two ``(B,Ecap)`` length tensors."""
+
+    def __init__(self, metric, consistent_topology=False):
+        super().__init__(consistent_topology)
+        self.metric = metric
+
+    def forward(self, vert1, vert2, face=None):
+        topo = self._topology(vert1, vert2, face)
+        sq1 = _mesh_edges.mesh_edge_sqrlen(vert1, topo)
+        sq2 = _mesh_edges.mesh_edge_sqrlen(vert2, topo)
+        loss = [self.metric(sq1[b, :topo.count(b)], sq2[b, :topo.count(b)]) for b in range(vert1.shape[0])]
+        return torch.mean(torch.stack(loss, dim=0))
+
+
+class MeshStretchLoss(_MeshTopologyLoss):
+    """Stretch only: ``max(sq2 / sq1 - 1, 0)`` on the SQUARED edge lengths of ``vert2`` over those of the reference
+    ``vert1``, no epsilon (reference :212-266): a zero-length reference edge gives inf or NaN as the division does.
+    Per batch element ``mean`` / ``max`` / ``sum``, then the mean over the batch; ``"none"``: the (B,) means."""
+
+    def __init__(self, reduction="mean", consistent_topology=False):
+        super().__init__(consistent_topology)
+        self.reduction = reduction
+
+    def forward(self, vert1, vert2, face=None):
+        if self.reduction not in ("mean", "none", "max", "sum"):
+            raise NotImplementedError
+        topo = self._topology(vert1, vert2, face)
+        sq1 = _mesh_edges.mesh_edge_sqrlen(vert1, topo)
+        sq2 = _mesh_edges.mesh_edge_sqrlen(vert2, topo)
+        # a padding row divides by 1, not by its own 0: its quotient is masked below, but its NaN gradient would not be
+        valid, _ = _edge_mask(topo, sq1)
+        sq1 = torch.where(valid, sq1, torch.ones_like(sq1))
+        stretch = torch.max(sq2 / sq1 - 1, torch.zeros_like(sq1))
+        return _reduce_edges(stretch, topo, self.reduction)
+
+
+class SimpleMeshRepulsionLoss(torch.nn.Module):
+    """``1 / (sq + 1e-6)`` over the edges whose SQUARED length ``sq`` is below ``threshold ** 2`` (reference :269-308:
+    the square goes into the comparison and into the reciprocal).  ``edges`` (E,2), shared by the batch; the argument
+    of ``forward`` overrides the constructor's.  Reductions as in MeshStretchLoss.  The ``MeshEdges`` of an edge
+    tensor is kept for as long as the same tensor, unmodified, comes back.  ``consistent_topology`` is accepted and,
+    as in the reference, unused."""
+
+    def __init__(self, threshold, edges=None, reduction="mean", consistent_topology=False):
+        super().__init__()
+        self.threshold2 = threshold * threshold
+        self.edges = edges
+        self.reduction = reduction
+        self._built = None   # (edge tensor, its _version, n_vertices, MeshEdges)
+
+    def _topology(self, edges, n_vertices):
+        built = self._built
+        if built is None or built[0] is not edges or built[1] != edges._version or built[2] != n_vertices:
+            built = (edges, edges._version, n_vertices, _mesh_edges.MeshEdges.from_edges(edges, n_vertices))
+            self._built = built
+        return built[3]
+
+    def forward(self, verts, edges=None):
+        if self.reduction not in ("mean", "none", "max", "sum"):
+            raise NotImplementedError
+        if edges is None:
+            edges = self.edges
+        assert(edges is not None)
+        topo = self._topology(edges, verts.shape[1])
+        sq = _mesh_edges.mesh_edge_sqrlen(verts, topo)
+        tmp = 1 / (sq + 1e-6)
+        tmp = torch.where(sq < self.threshold2, tmp, torch.zeros_like(tmp))
+        return _reduce_edges(tmp, topo, self.reduction)
