@@ -413,6 +413,38 @@ int pp_mesh_edge_sqrlen_backward_f32(const float* vertices, const long long* edg
                                      const unsigned* inc_entries, const float* grad_out, float* grad_vertices, int B,
                                      int N, int Ecap, int shared_topology, void* stream);
 
+/* ---- mesh Laplacians ------------------------------------------------------------------------
+ * What the reference's UniformLaplacian, CotLaplacian and cotangent (geo_operations.py:155-346) stand on; contract in
+ * DESIGN.md "Mesh Laplacians".  A corner is (f, c) with vertex faces[f,c], next = faces[f,(c+1)%L] and
+ * prev = faces[f,(c-1)%L].
+ * pp_mesh_corner_incidence: faces (Bt,F,L) int64, L >= 3 -> start (Bt,n_vertices+1) int32; codes (Bt,L*F) uint32:
+ *   vertex v's slice [start[v],start[v+1]) holds L*f + c for every corner with faces[f,c] == v, ascending; nbr
+ *   (Bt,L*F,2) int32: (next, prev) of every slot, -1 for an index outside [0,n_vertices).  flags (Bt) int32 is
+ *   overwritten: non-zero where a face names such an index, which is only compared and whose corner is left out (the
+ *   slots behind start[n_vertices] are then not written).  Scratch: pp_mesh_edges_workspace_bytes(Bt, n_vertices, L*F)
+ *   bytes, and the same limits.  Built with the bucket / scan / fill / sort chain of the edge builds.
+ * pp_mesh_cotangent_f32: vertices (B,N,3), triangles faces (Bt,F,3) -> out (B,F,3), columns for the edges 23, 31, 12:
+ *   l = sqrt((dx*dx + dy*dy) + dz*dz); sp = ((l1+l2)+l3)*0.5; inside = sp*(sp-l1)*(sp-l2)*(sp-l3) left to right,
+ *   negative -> 0; A = 2*sqrt(inside); out = ((l2*l2 + l3*l3) - l1*l1) / (A + 1e-10f) / 4 and its rotations, +0 where
+ *   A == 0.  A face with an index outside [0,N) reads nothing and gives NaN.
+ * pp_mesh_laplacian_apply_f32: out (B,N,3), overwritten; one gather per vertex over its slice in slot order, from +0,
+ *   plain fp32 operations: no floating-point atomics, the same bits on every run.
+ *   mode 0, uniform forward:  acc += (x_i - x_next); acc += (x_i - x_prev); out = acc / ((float)(2n) + 1e-12f), n the
+ *     number of slots of i.
+ *   mode 1, uniform backward: x is the incoming gradient g; the same sum over h_k = g_k / ((float)(2 n_k) + 1e-12f),
+ *     not divided again (exact: the half-edge multiplicity matrix is symmetric).
+ *   mode 2, cotangent (L == 3), weights (B,F,3): for a slot 3f + c, acc += W[b,f,(c+2)%3] * (x_next - x_i);
+ *     acc += W[b,f,(c+1)%3] * (x_prev - x_i).  The operator is symmetric: its backward is mode 2 on the gradient.
+ *   weights may be NULL in modes 0 and 1.  shared_topology != 0: start, codes and nbr have one batch element, read by
+ *   every b; weights are always per batch element.  A neighbour stored as -1 adds NaN. */
+int pp_mesh_corner_incidence(const long long* faces, int* start, unsigned* codes, int* nbr, int* flags, int Bt, int F,
+                             int L, int n_vertices, void* workspace, size_t workspace_bytes, void* stream);
+int pp_mesh_cotangent_f32(const float* vertices, const long long* faces, float* out, int B, int N, int F,
+                          int shared_topology, void* stream);
+int pp_mesh_laplacian_apply_f32(const float* x, const int* start, const int* nbr, const unsigned* codes,
+                                const float* weights, float* out, int B, int N, int F, int L, int mode,
+                                int shared_topology, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -90,6 +90,9 @@ SIGNATURES = {
     "pp_mesh_edge_incidence": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
     "pp_mesh_edge_sqrlen_forward_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "pp_mesh_edge_sqrlen_backward_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_mesh_corner_incidence": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_mesh_cotangent_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_mesh_laplacian_apply_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_bytes": _c_size_t,
              "pp_nmdistance_forward_workspace_bytes": _c_size_t,

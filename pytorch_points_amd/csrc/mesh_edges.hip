@@ -24,6 +24,14 @@
 //
 // An index outside [0, n_vertices) is never used as an address: the builds only compare it, skip what it belongs to and
 // set the batch element's flag word (the host raises); the forward writes NaN for such an edge and the backward adds NaN.
+//
+// The mesh Laplacians (geo_operations.py:155-346: UniformLaplacian, CotLaplacian, cotangent) stand on the same chain:
+//   corner incidence   faces (Bt,F,L) -> for every vertex the list of L*f + c over the corners with faces[f,c] == v,
+//                      ascending, and beside every slot its corner's (next, prev) vertices as int32
+//   cotangent          one thread per face, the reference's operation order in fp32
+//   apply              one thread per (b, vertex): a gather over the vertex's slice from +0 in slot order, plain fp32
+//                      operations; the uniform operator's forward and backward and the cotangent operator (whose
+//                      backward is the same call on the gradient) are three modes of one kernel
 #include "pp_common.h"
 
 namespace {
@@ -330,6 +338,180 @@ __global__ __launch_bounds__(kMeThreads) void me_sqrlen_backward_kernel(
   grad[i * 3 + 2] = az;
 }
 
+// ---- corners ------------------------------------------------------------------------------------------------------
+// One thread per corner (b, f, c) of faces (Bt,F,L).  FILL = false: the vertices' corner counts; FILL = true: the lists
+// receive L*f + c.  A corner outside [0, N) sets the flag and takes no part.
+template <bool FILL>
+__global__ __launch_bounds__(kMeThreads) void me_corners_kernel(const long long* __restrict__ faces,
+                                                                unsigned* __restrict__ cursor,
+                                                                unsigned* __restrict__ entries,
+                                                                int* __restrict__ flags, long long total,
+                                                                long long X, int N) {
+  const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long b = x / X;
+  const long long v = faces[x];
+  if (v < 0 || v >= N) {
+    if (!FILL) atomicOr(flags + b, 1);
+    return;
+  }
+  unsigned* cur = cursor + (size_t)b * N + (size_t)v;
+  if (!FILL) {
+    atomicAdd(cur, 1u);
+  } else {
+    const unsigned pos = atomicAdd(cur, 1u);   // < L*F
+    entries[(size_t)b * X + pos] = (unsigned)(x - b * X);
+  }
+}
+
+// One thread per slot of the sorted lists: (next, prev) of the slot's corner, -1 for a vertex outside [0, N), so that
+// the apply reads its neighbours beside each other and never follows a 64-bit face row
+__global__ __launch_bounds__(kMeThreads) void me_corner_nbr_kernel(const long long* __restrict__ faces,
+                                                                   const int* __restrict__ start,
+                                                                   const unsigned* __restrict__ codes,
+                                                                   int* __restrict__ nbr, long long total, long long X,
+                                                                   int L, int N) {
+  const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long b = x / X;
+  const long long q = x - b * X;
+  if (q >= start[b * ((long long)N + 1) + N]) return;   // behind the last slice (corners that were out of range)
+  const unsigned code = codes[x];
+  if ((long long)code >= X) return;
+  const unsigned f = code / (unsigned)L, c = code - f * (unsigned)L;
+  const long long* __restrict__ row = faces + b * X + (long long)f * L;
+  const long long nx = row[c + 1 == (unsigned)L ? 0 : c + 1], pv = row[c == 0 ? L - 1 : c - 1];
+  nbr[2 * x] = (nx < 0 || nx >= N) ? -1 : (int)nx;
+  nbr[2 * x + 1] = (pv < 0 || pv >= N) ? -1 : (int)pv;
+}
+
+// ---- cotangent ----------------------------------------------------------------------------------------------------
+// One thread per face: geo_operations.py:306-346 step for step (the build does not contract a*b + c).  A face with an
+// index outside [0, N) writes NaN and reads nothing.
+__global__ __launch_bounds__(kMeThreads) void me_cotangent_kernel(const float* __restrict__ vertices,
+                                                                  const long long* __restrict__ faces,
+                                                                  float* __restrict__ out, long long total, int N,
+                                                                  int F, int shared) {
+  const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long b = x / F;
+  const long long* __restrict__ row = faces + (shared ? x - b * F : x) * 3;
+  const long long i1 = row[0], i2 = row[1], i3 = row[2];
+  float* __restrict__ o = out + x * 3;
+  if (i1 < 0 || i1 >= N || i2 < 0 || i2 >= N || i3 < 0 || i3 >= N) {
+    o[0] = o[1] = o[2] = me_nan();
+    return;
+  }
+  const float* __restrict__ vb = vertices + (size_t)b * N * 3;
+  const float* __restrict__ p1 = vb + i1 * 3;
+  const float* __restrict__ p2 = vb + i2 * 3;
+  const float* __restrict__ p3 = vb + i3 * 3;
+  auto len = [](const float* __restrict__ p, const float* __restrict__ q) {
+    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+    return sqrtf((dx * dx + dy * dy) + dz * dz);   // correctly rounded in this build
+  };
+  const float l1 = len(p2, p3), l2 = len(p3, p1), l3 = len(p1, p2);
+  const float sp = ((l1 + l2) + l3) * 0.5f;
+  float inside = ((sp * (sp - l1)) * (sp - l2)) * (sp - l3);
+  if (inside < 0.0f) inside = 0.0f;
+  const float A = 2.0f * sqrtf(inside);
+  if (A == 0.0f) {
+    o[0] = o[1] = o[2] = 0.0f;
+    return;
+  }
+  const float s1 = l1 * l1, s2 = l2 * l2, s3 = l3 * l3, den = A + 1e-10f;
+  o[0] = (((s2 + s3) - s1) / den) / 4.0f;
+  o[1] = (((s1 + s3) - s2) / den) / 4.0f;
+  o[2] = (((s1 + s2) - s3) / den) / 4.0f;
+}
+
+// ---- the Laplacian apply ------------------------------------------------------------------------------------------
+// One thread per (b, vertex i), its slice in ascending slot order, acc from +0, every operation rounded as written.
+//   MODE 0  uniform forward    acc += (x_i - x_next); acc += (x_i - x_prev);  out = acc / ((float)(2n) + 1e-12f)
+//   MODE 1  uniform backward   the same sum over h_k = g_k / ((float)(2 n_k) + 1e-12f), not divided again.
+//           The forward is out = D^-1 M x with D = diag(2n + 1e-12) and (M x)_i = sum over the slots at i of
+//           (x_i - x_next) + (x_i - x_prev), so M = diag(2n) - W with W_ij = h(i,j) + h(j,i), h(p,q) the number of
+//           half-edges p -> q (a slot at i with prev == j is a half-edge j -> i).  W, hence M, is symmetric, and
+//           grad = (D^-1 M)^T g = M (D^-1 g) = M h: the forward's gather over h.  n_k is the length of k's own slice.
+//   MODE 2  cotangent          slot code 3f + c: acc += W[b,f,(c+2)%3] * (x_next - x_i); acc += W[b,f,(c+1)%3] *
+//           (x_prev - x_i).  L is symmetric and constant: the backward is this mode on the gradient.
+// A neighbour outside [0, N) (the build stored -1) is not read: NaN is added.
+template <int MODE>
+__global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
+    const float* __restrict__ x, const int* __restrict__ start, const int* __restrict__ nbr,
+    const unsigned* __restrict__ codes, const float* __restrict__ weights, float* __restrict__ out, long long rows,
+    int N, int F, long long X, int shared) {
+  const long long r = (long long)blockIdx.x * kMeThreads + threadIdx.x;
+  if (r >= rows) return;
+  const long long b = r / N;
+  const long long i = r - b * N;
+  const long long tb = shared ? 0 : b;
+  const float* __restrict__ xb = x + (size_t)b * N * 3;
+  const int* __restrict__ st = start + (size_t)tb * ((size_t)N + 1);
+  const int2* __restrict__ nb = reinterpret_cast<const int2*>(nbr) + (size_t)tb * (size_t)X;
+  const unsigned* __restrict__ cd = codes + (size_t)tb * (size_t)X;
+  const float* __restrict__ wb = weights + (size_t)b * F * 3;
+  const int q0 = st[i], q1 = st[i + 1];
+  float px = xb[i * 3], py = xb[i * 3 + 1], pz = xb[i * 3 + 2];
+  if (MODE == 1) {
+    const float d = (float)(2 * (q1 - q0)) + 1e-12f;
+    px = px / d;
+    py = py / d;
+    pz = pz / d;
+  }
+  float ax = 0.0f, ay = 0.0f, az = 0.0f;
+  for (int q = q0; q < q1; ++q) {
+    const int2 jk = nb[q];
+    float w[2] = {1.0f, 1.0f};
+    if (MODE == 2) {
+      const unsigned code = cd[q];
+      const unsigned f = code / 3u, c = code - f * 3u;
+      if (f < (unsigned)F) {
+        w[0] = wb[(size_t)f * 3 + (c == 0 ? 2 : c - 1)];   // (c + 2) % 3
+        w[1] = wb[(size_t)f * 3 + (c == 2 ? 0 : c + 1)];   // (c + 1) % 3
+      } else {
+        w[0] = w[1] = me_nan();
+      }
+    }
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      const int j = side ? jk.y : jk.x;
+      float ox, oy, oz;
+      if (j < 0 || j >= N) {
+        ox = oy = oz = me_nan();
+      } else {
+        ox = xb[(size_t)j * 3];
+        oy = xb[(size_t)j * 3 + 1];
+        oz = xb[(size_t)j * 3 + 2];
+        if (MODE == 1) {
+          const float d = (float)(2 * (st[j + 1] - st[j])) + 1e-12f;
+          ox = ox / d;
+          oy = oy / d;
+          oz = oz / d;
+        }
+      }
+      if (MODE == 2) {
+        ax = ax + w[side] * (ox - px);
+        ay = ay + w[side] * (oy - py);
+        az = az + w[side] * (oz - pz);
+      } else {
+        ax = ax + (px - ox);
+        ay = ay + (py - oy);
+        az = az + (pz - oz);
+      }
+    }
+  }
+  if (MODE == 0) {
+    const float d = (float)(2 * (q1 - q0)) + 1e-12f;
+    ax = ax / d;
+    ay = ay / d;
+    az = az / d;
+  }
+  out[r * 3] = ax;
+  out[r * 3 + 1] = ay;
+  out[r * 3 + 2] = az;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------
 // the index words in use: u32 positions and codes within a batch element, int32 starts, 31-bit grids
 bool me_build_ok(int Bt, int N, long long items) {
@@ -470,6 +652,82 @@ extern "C" int pp_mesh_edge_sqrlen_backward_f32(const float* vertices, const lon
   const long long rows = (long long)B * N;
   me_sqrlen_backward_kernel<<<dim3(me_blocks(rows, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
       vertices, edges, inc_start, inc_entries, grad_out, grad_vertices, rows, N, Ecap, shared_topology != 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_corner_incidence(const long long* faces, int* start, unsigned* codes, int* nbr, int* flags,
+                                        int Bt, int F, int L, int n_vertices, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  const int N = n_vertices;
+  if (F < 0 || L < 3) return PP_EINVAL;
+  const long long X = (long long)L * F;
+  if (!me_build_ok(Bt, N, X) || (long long)Bt * ((long long)N + 1) > 0x7fffffffLL) return PP_EINVAL;
+  if (Bt == 0) return PP_OK;
+  if (!start || !flags) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = pp::fill_bytes(flags, 0, 4 * (size_t)Bt, s);
+  if (e != hipSuccess) return (int)e;
+  if (F == 0 || N == 0) {   // no list has an entry; a corner of a mesh without vertices is out of range
+    e = pp::fill_bytes(start, 0, 4 * (size_t)Bt * ((size_t)N + 1), s);
+    if (e != hipSuccess) return (int)e;
+    if (F == 0) return PP_OK;
+    return (int)pp::fill_bytes(flags, 1, 4 * (size_t)Bt, s);   // (any non-zero word)
+  }
+  const MeLayout lay = me_layout(Bt, N, X);
+  unsigned char* ws = (unsigned char*)workspace;
+  if (!faces || !codes || !nbr || !ws || workspace_bytes < lay.entries) return PP_EINVAL;   // the lists are built in place
+  unsigned* cursor = reinterpret_cast<unsigned*>(ws + lay.cursor);
+  unsigned* st = reinterpret_cast<unsigned*>(ws + lay.start);
+  e = pp::fill_bytes(ws, 0, lay.start, s);
+  if (e != hipSuccess) return (int)e;
+  const long long total = (long long)Bt * X;
+  me_corners_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, codes, flags,
+                                                                                            total, X, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_scan_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, st, start, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  me_corners_kernel<true><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, codes, flags,
+                                                                                           total, X, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  const int rc = me_sort_buckets(ws, lay, codes, Bt, N, X, s);
+  if (rc != PP_OK) return rc;
+  me_corner_nbr_kernel<<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, start, codes, nbr, total,
+                                                                                        X, L, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_cotangent_f32(const float* vertices, const long long* faces, float* out, int B, int N, int F,
+                                     int shared_topology, void* stream) {
+  if (B < 0 || N < 0 || F < 0 || (long long)B * F > 0x7fffffffLL || (long long)B * N > 0x7fffffffLL) return PP_EINVAL;
+  if (B == 0 || F == 0) return PP_OK;
+  if (!faces || !out || (N > 0 && !vertices)) return PP_EINVAL;
+  const long long total = (long long)B * F;
+  me_cotangent_kernel<<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
+      vertices, faces, out, total, N, F, shared_topology != 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_laplacian_apply_f32(const float* x, const int* start, const int* nbr, const unsigned* codes,
+                                           const float* weights, float* out, int B, int N, int F, int L, int mode,
+                                           int shared_topology, void* stream) {
+  if (B < 0 || N < 0 || F < 0 || L < 3 || mode < 0 || mode > 2 || (mode == 2 && L != 3)) return PP_EINVAL;
+  const long long X = (long long)L * F;
+  if ((long long)B * N > 0x7fffffffLL || X > 0x7fffffffLL) return PP_EINVAL;
+  if (B == 0 || N == 0) return PP_OK;
+  if (!x || !start || !out || (F > 0 && (!nbr || !codes || (mode == 2 && !weights)))) return PP_EINVAL;
+  const long long rows = (long long)B * N;
+  const dim3 grid(me_blocks(rows, kMeThreads)), block(kMeThreads);
+  hipStream_t s = (hipStream_t)stream;
+  const int sh = shared_topology != 0;
+  if (mode == 0)
+    me_laplacian_apply_kernel<0><<<grid, block, 0, s>>>(x, start, nbr, codes, weights, out, rows, N, F, X, sh);
+  else if (mode == 1)
+    me_laplacian_apply_kernel<1><<<grid, block, 0, s>>>(x, start, nbr, codes, weights, out, rows, N, F, X, sh);
+  else
+    me_laplacian_apply_kernel<2><<<grid, block, 0, s>>>(x, start, nbr, codes, weights, out, rows, N, F, X, sh);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }

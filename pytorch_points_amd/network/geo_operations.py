@@ -2,14 +2,18 @@
 furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
 (:88-126), the cage coordinates mean_value_coordinates_3D (:349-456) and green_coordinates_3D (:625-773), and the
 face normals those need, compute_face_normals_and_areas (:529-559), the point-cloud Laplacian
-pointUniformLaplacian (:128-152), and the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600).
+pointUniformLaplacian (:128-152), the mesh Laplacians UniformLaplacian, CotLaplacian and cotangent (:155-346), and
+the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600).
 The other mesh-geometry functions of that file are out of scope."""
+import collections
+
 import numpy as np
 import torch
 
 from .. import green as _green
 from .. import knn_edges as _knn_edges
 from .. import mesh_edges as _mesh_edges
+from .. import mesh_laplacian as _mesh_laplacian
 from .. import mvc as _mvc
 from .. import ops
 from .._ext import sampling
@@ -187,3 +191,79 @@ def get_edge_lengths(vertices, edge_points):
     ends = vertices[edge_points[:, :2]]
     t = ends[:, 0, :] - ends[:, 1, :]
     return torch.sum(t * t, dim=-1)
+
+
+# ------------------------------------------------------------------------------------------- mesh Laplacians
+class UniformLaplacian(torch.nn.Module):
+    """Uniform Laplacian of a mesh (reference :155-205): ``verts`` (B,N,D), ``faces`` (B,F,L) of any degree L >= 3 ->
+    ``L verts / (Lii + 1e-12)`` (B,N,D), with half-edge multiplicities as weights.
+
+    ``self.L`` is built on the first call that finds it None (``faces`` is required then) and kept; assigning
+    ``laplacian.L = None`` resets it.  It is a ``pytorch_points_amd.mesh_laplacian.MeshCorners`` -- the sorted
+    vertex -> corner lists -- not a sparse matrix; ``self.Lii`` is the reference's (Bt*N,) tensor of ``2 * #corners``.
+    An ``L`` built from a single mesh serves a batch (the reference's ``self.L.shape[0] != B*N`` branch).  The build
+    makes one device-to-host copy; nothing afterwards touches the host."""
+
+    def __init__(self):
+        super().__init__()
+        self.L = None
+
+    def computeLaplacian(self, V, F):
+        self.L = _mesh_laplacian.MeshCorners.from_faces(F.to(V.device), V.shape[1])
+        self.Lii = self.L.lii(V.dtype)
+
+    def forward(self, verts, faces=None):
+        if self.L is None:
+            assert(faces is not None)
+            self.computeLaplacian(verts, faces)
+        if self.L.batch != verts.shape[0]:
+            # during initialization, used a single batch point set
+            assert(self.L.batch == 1)
+        return _mesh_laplacian.mesh_uniform_laplacian(verts, self.L)
+
+
+CotOperator = collections.namedtuple("CotOperator", ["corners", "weights"])
+CotOperator.__doc__ = """what ``CotLaplacian.L`` holds: the ``MeshCorners`` of the faces and the detached cotangents
+(B,F,3) of the vertices that built it"""
+
+
+class CotLaplacian(torch.nn.Module):
+    """Cotangent Laplacian of a triangle mesh (reference :218-304): ``V`` (B,N,3), ``F`` (B,F,3) -> ``L V`` (B,N,3).
+
+    ``self.L`` is built on the first call that finds it None (``F`` is required then) from THAT call's ``V`` and kept:
+    the operator is a constant, later calls reuse its cotangents whatever their ``V``, and the backward is the same
+    operator applied to the incoming gradient.  Assigning ``laplacian.L = None`` resets it.  It is a ``CotOperator``
+    (corner lists and cotangents on the device), not a scipy matrix, and every apply, forward and backward, stays on
+    the device.  The build makes two device-to-host copies: the topology's out-of-range flags and the reference's
+    ``check_values`` of the cotangents, which raises ValueError here on a non-finite cotangent (the reference
+    asserts); nothing afterwards touches the host.  Unlike the reference's, the build does not print.  The output's
+    ``requires_grad`` follows ``V``'s."""
+
+    def __init__(self):
+        super().__init__()
+        self.L = None
+
+    def computeLaplacian(self, V, F):
+        F = F.detach()
+        if F.shape[-1] != 3:
+            raise NotImplementedError("CotLaplacian: triangles only, got faces of %d corners" % F.shape[-1])
+        corners = _mesh_laplacian.MeshCorners.from_faces(F.to(V.device), V.shape[1])
+        C = cotangent(V.detach(), corners.faces).detach()
+        if not bool(torch.isfinite(C).all()):          # the reference's assert(check_values(C)); once per build
+            raise ValueError("CotLaplacian: the cotangents of the mesh are not all finite")
+        self.L = CotOperator(corners, C)
+
+    def forward(self, V, F=None):
+        if self.L is None:
+            assert(F is not None)
+            self.computeLaplacian(V, F)
+        return _mesh_laplacian.mesh_cot_laplacian(V, self.L.corners, self.L.weights)
+
+
+def cotangent(V, F):
+    """Cotangents ``C`` (B,F,3) of the angles of the triangles ``F`` (B,F,3) over ``V`` (B,N,3), columns for the edges
+    23, 31, 12 (reference :306-346): Heron's area, ``(l_a^2 + l_b^2 - l_c^2) / (A + 1e-10) / 4``, exactly 0 for a face
+    without area.  CUDA fp32 runs the HIP kernel when no gradient to ``V`` is asked for (``CotLaplacian`` detaches);
+    with ``V.requires_grad``, and on other devices and dtypes, the same formula as torch operations
+    (pytorch_points_amd.mesh_laplacian)."""
+    return _mesh_laplacian.cotangent(V, F)

@@ -2,8 +2,9 @@
 nndistance and LabeledNmdistanceFunction / labeled_nndistance (reference network/model_loss.py:401-483), and the
 point-cloud regularisers PointLaplacianLoss, PointEdgeLengthLoss, PointStretchLoss, SmapeLoss, NormalLoss and
 SimplePointRepulsionLoss (:73-163, :310-398) over pytorch_points_amd.knn_edges, and the mesh edge losses
-MeshEdgeLengthLoss, MeshStretchLoss and SimpleMeshRepulsionLoss (:166-308) over pytorch_points_amd.mesh_edges.  The
-Laplacian mesh losses of that file are out of scope.
+MeshEdgeLengthLoss, MeshStretchLoss and SimpleMeshRepulsionLoss (:166-308) over pytorch_points_amd.mesh_edges, and
+the mesh Laplacian losses UniformLaplacianSmoothnessLoss and MeshLaplacianLoss (:8-71) over
+pytorch_points_amd.mesh_laplacian.
 
 ``nndistance`` / ``labeled_nndistance`` are the C++ autograd nodes of csrc/torch_bridge.cpp (the reference's
 host side is a C++ extension too): at config 2 the step's kernels take less time than Python needs to issue
@@ -408,3 +409,76 @@ class SimpleMeshRepulsionLoss(torch.nn.Module):
         tmp = 1 / (sq + 1e-6)
         tmp = torch.where(sq < self.threshold2, tmp, torch.zeros_like(tmp))
         return _reduce_edges(tmp, topo, self.reduction)
+
+
+# ---------------------------------------------------------------------------------------- mesh Laplacian losses
+# The reference's modules (:8-71) with their control flow as written, quirks included (DESIGN.md "Mesh Laplacians"
+# lists them).  The Laplacians are geo_operations.UniformLaplacian / CotLaplacian: a topology object built with one
+# host read, then one launch per apply.
+class UniformLaplacianSmoothnessLoss(torch.nn.Module):
+    """Encourages minimal mean curvature shapes (reference :8-27): the norm (B,N) of the uniform Laplacian of ``vert``
+    over the constructor's ``faces``.  With ``vert_ref`` the reference curvature is computed from ``vert`` again, as in
+    the reference, so the result is ``metric(curve, curve)``.  ``num_point`` is unused there too.  The topology is
+    built by the first call and kept."""
+
+    def __init__(self, num_point, faces, metric):
+        super().__init__()
+        from . import geo_operations as geo_op
+        self.laplacian = geo_op.UniformLaplacian()
+        self.metric = metric
+        self.faces = faces
+
+    def forward(self, vert, vert_ref=None):
+        lap = self.laplacian(vert, self.faces)
+        curve = torch.norm(lap, p=2, dim=-1)
+        if vert_ref is not None:
+            lap_ref = self.laplacian(vert, self.faces)
+            curve_gt = torch.norm(lap_ref, p=2, dim=-1)
+            loss = self.metric(curve, curve_gt)
+        else:
+            loss = curve
+        return loss
+
+
+class MeshLaplacianLoss(torch.nn.Module):
+    """``metric`` between the Laplacians of two meshes of one connectivity in correspondence (reference :29-71).
+    ``use_cot``: the cotangent Laplacian instead of the uniform one; ``use_norm``: compare the norms (B,N);
+    ``consistent_topology``: keep the Laplacian of the first call (and then no call after it touches the host);
+    ``precompute_L``: keep the first call's ``lap1`` in ``self.L``.  Without ``consistent_topology`` the Laplacian is
+    rebuilt at the start of every call, so a call's cotangent weights come from ``vert1`` and serve ``vert2`` as well
+    -- or come from ``vert2`` when ``lap1`` is the kept one.  ``vert2=None`` returns ``lap1.mean()``; the reference's
+    ``assert(~self.precompute_L)`` there never fires (``~True`` is -2) and is not kept."""
+
+    def __init__(self, metric, use_cot=False, use_norm=False, consistent_topology=False, precompute_L=False):
+        super().__init__()
+        from . import geo_operations as geo_op
+        if use_cot:
+            self.laplacian = geo_op.CotLaplacian()
+        else:
+            self.laplacian = geo_op.UniformLaplacian()
+        self.use_norm = use_norm
+        self.consistent_topology = consistent_topology
+        self.metric = metric
+        self.precompute_L = precompute_L
+        self.L = None
+
+    def forward(self, vert1, vert2=None, face=None):
+        if not self.consistent_topology:
+            self.laplacian.L = None
+
+        if self.L is None or (not self.precompute_L):
+            lap1 = self.laplacian(vert1, face)
+            if self.use_norm:
+                lap1 = torch.norm(lap1, dim=-1, p=2)
+            if self.precompute_L:
+                self.L = lap1
+        else:
+            lap1 = self.L
+
+        if vert2 is not None:
+            lap2 = self.laplacian(vert2, face)
+            if self.use_norm:
+                lap2 = torch.norm(lap2, dim=-1, p=2)
+            return self.metric(lap1, lap2)
+        else:
+            return lap1.mean()
