@@ -349,6 +349,30 @@ int pp_gc3d_backward_f64(const double* query, const double* vertices, const long
                          const double* grad_gc_face, double* grad_query, double* grad_normals, int B, int P, int N,
                          int F, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mean value coordinates, 2-D -----------------------------------------------------------
+ * Replaces network.geo_operations.mean_value_coordinates(points, polygon) (geo_operations.py:459-526, torch
+ * composition); contract in DESIGN.md "Mean value coordinates, 2-D".  Channel-first: points (B,2,N), polygon (B,2,M),
+ * vertices i+1 and i-1 taken cyclically; any M.  Forward -> phi (B,M,N) normalised weights; w (B,M,N), nullable, the
+ * row before the division; sums (B,N) the divisor used; codes (B,N) int32 branch bits (1 zero row sum, 2 on an edge,
+ * 4 on a vertex, 8 a non-finite input: the row is NaN).  Backward: grad_phi (B,M,N), grad_w (nullable) ->
+ * grad_points (B,2,N), grad_polygon (B,2,M), with a workspace of pp_mvc2d_workspace_bytes(B,N,M,sizeof element) bytes
+ * (0 for an element size that is not served).  A size of zero is served: the forward then writes nothing, the backward
+ * zero gradients; a negative size returns PP_EINVAL before any pointer is looked at.  No floating-point atomics:
+ * every output is reproducible bit for bit, and a query's row does not depend on the other queries. */
+size_t pp_mvc2d_workspace_bytes(int B, int N, int M, int elem_bytes);
+int pp_mvc2d_forward_f32(const float* points, const float* polygon, float* phi, float* w, float* sums, int* codes,
+                         int B, int N, int M, void* stream);
+int pp_mvc2d_forward_f64(const double* points, const double* polygon, double* phi, double* w, double* sums, int* codes,
+                         int B, int N, int M, void* stream);
+int pp_mvc2d_backward_f32(const float* points, const float* polygon, const float* phi, const float* sums,
+                          const int* codes, const float* grad_phi, const float* grad_w, float* grad_points,
+                          float* grad_polygon, int B, int N, int M, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int pp_mvc2d_backward_f64(const double* points, const double* polygon, const double* phi, const double* sums,
+                          const int* codes, const double* grad_phi, const double* grad_w, double* grad_points,
+                          double* grad_polygon, int B, int N, int M, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* ---- k-NN edge operators -------------------------------------------------------------------
  * The (B,N,K,D) gather of a cloud's k-NN neighbourhoods and what the reference's point-cloud regularisers compute
  * from it, without the gather; contract in DESIGN.md "k-NN edge operators".  points (B,N,D) fp32, idx int64 (B,N,K) as

@@ -5,6 +5,7 @@
     from pytorch_points.network.operations import QueryAndGroup, gather_points, ball_query, batch_svd
     from pytorch_points.network.geo_operations import furthest_point_sample, batch_normals, mean_value_coordinates_3D
     from pytorch_points.network.geo_operations import green_coordinates_3D, compute_face_normals_and_areas
+    from pytorch_points.network.geo_operations import mean_value_coordinates
     from pytorch_points.network.pointnet2_utils import three_nn, three_interpolate
     from pytorch_points._ext import losses, sampling, linalg
 

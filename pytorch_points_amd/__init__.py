@@ -3,14 +3,16 @@
 Drop-in for the reference's operator API on that path only:
     pytorch_points.network.model_loss.{nndistance, labeled_nndistance, the point-cloud regularisers,
         MeshEdgeLengthLoss, MeshStretchLoss, SimpleMeshRepulsionLoss}
-    pytorch_points.network.operations.{gather_points, ball_query, grouping_operation, QueryAndGroup, batch_svd}
+    pytorch_points.network.operations.{gather_points, ball_query, grouping_operation, QueryAndGroup, batch_svd,
+        normalize, sqrNorm, dot_product, cross_product_2D}
     pytorch_points.network.geo_operations.{furthest_point_sample, batch_normals, mean_value_coordinates_3D,
-        green_coordinates_3D, compute_face_normals_and_areas, pointUniformLaplacian, edge_vertex_indices,
+        mean_value_coordinates, green_coordinates_3D, compute_face_normals_and_areas, pointUniformLaplacian, edge_vertex_indices,
         get_edge_lengths}
     pytorch_points.network.pointnet2_utils.{three_nn, three_interpolate, QueryAndGroup, GroupAll}
     pytorch_points._ext.{losses, sampling, linalg}
-mean_value_coordinates_3D and green_coordinates_3D also accept CPU tensors and other dtypes, through torch
-compositions of their contracts (pytorch_points_amd.mvc.composition, pytorch_points_amd.green.composition).
+mean_value_coordinates_3D, mean_value_coordinates and green_coordinates_3D also accept CPU tensors and other dtypes,
+through torch compositions of their contracts (pytorch_points_amd.mvc.composition, pytorch_points_amd.mvc2d.composition,
+pytorch_points_amd.green.composition).
 Host code is Python on PyTorch-ROCm (device memory, streams, torch.distributed); the kernels are
 hand-written HIP in csrc/, reached through the C ABI of libpp_hip.so (include/pp_hip.h).
 """

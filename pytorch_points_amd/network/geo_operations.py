@@ -1,10 +1,11 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
 furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
-(:88-126), the cage coordinates mean_value_coordinates_3D (:349-456) and green_coordinates_3D (:625-773), and the
+(:88-126), the cage coordinates mean_value_coordinates_3D (:349-456), mean_value_coordinates (:459-526, the 2-D
+polygon cage) and green_coordinates_3D (:625-773), and the
 face normals those need, compute_face_normals_and_areas (:529-559), the point-cloud Laplacian
 pointUniformLaplacian (:128-152), the mesh Laplacians UniformLaplacian, CotLaplacian and cotangent (:155-346), and
 the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600).
-The other mesh-geometry functions of that file are out of scope."""
+The remaining names of that file do not work in the reference either."""
 import collections
 
 import numpy as np
@@ -15,6 +16,7 @@ from .. import knn_edges as _knn_edges
 from .. import mesh_edges as _mesh_edges
 from .. import mesh_laplacian as _mesh_laplacian
 from .. import mvc as _mvc
+from .. import mvc2d as _mvc2d
 from .. import ops
 from .._ext import sampling
 from .operations import batch_svd, gather_points
@@ -119,6 +121,14 @@ def mean_value_coordinates_3D(query, vertices, faces, verbose=False):
     per-face weights.  CUDA fp32 / fp64 run fused HIP kernels; other devices and dtypes a torch composition of the
     same contract (pytorch_points_amd.mvc, DESIGN.md "Mean value coordinates")."""
     return _mvc.mean_value_coordinates_3D(query, vertices, faces, verbose)
+
+
+def mean_value_coordinates(points, polygon, verbose=False):
+    """Mean value coordinates (Floater 2003) of ``points`` (B,2,N) with respect to the closed polygon ``polygon``
+    (B,2,M), channel-first: ``phi`` (B,M,N), and ``(phi, w)`` with ``verbose``, ``w`` (B,M,N) the weights before the
+    division.  CUDA fp32 / fp64 run fused HIP kernels; other devices and dtypes a torch composition of the same
+    contract (pytorch_points_amd.mvc2d, DESIGN.md "Mean value coordinates, 2-D")."""
+    return _mvc2d.mean_value_coordinates(points, polygon, verbose)
 
 
 def compute_face_normals_and_areas(vertices, faces):

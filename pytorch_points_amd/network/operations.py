@@ -1,6 +1,8 @@
 """``pytorch_points.network.operations`` -- the part on the hot path: gather_points, ball_query,
-grouping_operation, QueryAndGroup (reference: network/operations.py:38-213), and batch_svd (:215-258).
-channel_shuffle, jitter and the torch one-liners of that file are out of scope."""
+grouping_operation, QueryAndGroup (reference: network/operations.py:38-213), and batch_svd (:215-258), and the
+four vector helpers that callers of mean_value_coordinates import beside it: normalize, sqrNorm, dot_product and
+cross_product_2D (:260-275).  channel_shuffle, jitter and the other torch one-liners of that file are out of scope
+(SURVEY.md §2.1)."""
 import torch
 
 from .._ext import linalg, sampling
@@ -170,3 +172,29 @@ def batch_svd(x):
     V (B,N,k), k = min(M, N) (reference operations.py:248-258)."""
     assert(x.dim() == 3)
     return BatchSVDFunction.apply(x)
+
+
+# ------------------------------------------------------------------------------------------- vector helpers
+def normalize(tensor, dim=-1):
+    """``tensor`` scaled to unit L2 length along ``dim`` (lengths below 1e-12 divide by 1e-12)"""
+    return torch.nn.functional.normalize(tensor, p=2.0, dim=dim, eps=1e-12)
+
+
+def sqrNorm(tensor, dim=-1, keepdim=False):
+    """squared L2 length along ``dim``"""
+    return (tensor * tensor).sum(dim=dim, keepdim=keepdim)
+
+
+def dot_product(tensor1, tensor2, dim=-1, keepdim=False):
+    """inner product along ``dim``"""
+    return (tensor1 * tensor2).sum(dim=dim, keepdim=keepdim)
+
+
+def cross_product_2D(tensor1, tensor2, dim=1):
+    """z component ``x1 y2 - y1 x2`` of the cross product of 2-vectors stored along ``dim``; ``dim`` is dropped"""
+    if tensor1.shape[dim] != 2 or tensor2.shape[dim] != 2:
+        raise AssertionError("cross_product_2D: both tensors need size 2 along dim %d, got %d and %d"
+                             % (dim, tensor1.shape[dim], tensor2.shape[dim]))
+    x1, y1 = tensor1.unbind(dim)
+    x2, y2 = tensor2.unbind(dim)
+    return x1 * y2 - y1 * x2
