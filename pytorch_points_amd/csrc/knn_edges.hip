@@ -4,10 +4,10 @@
 //   uniform Laplacian  lap[b,n,:] = -(sum_k points[b,idx[b,n,k],:]) / K + points[b,n,:]
 // The reference materialises the (B,N,K,D) gather through a (B,N,K,D) int64 index expansion and scatters the same
 // amount back in the backward.  Here no edge ever exists in memory: the forwards are one pass over idx, and the
-// backwards are GATHERS.  Once per backward call the reverse adjacency of idx is built (in-degrees with integer
-// atomics, a scan per batch element, a fill through integer cursors), and every point then adds its own centre term
+// backwards are GATHERS.  Once per backward call the reverse adjacency of idx is built (bucket_lists.h's chain: every
+// point's bucket receives the numbers n*K+k of its incoming edges), and every point then adds its own centre term
 // (ascending k) followed by the terms of its incoming edges.  No floating-point atomics in any form.  `ordered` sorts
-// every incoming list by edge number n*K+k first, so that the sum is the one a sequential loop over (n, k) makes:
+// every incoming list by edge number first, so that the sum is the one a sequential loop over (n, k) makes:
 // reproducible bit for bit (torch.use_deterministic_algorithms).  Without it a list keeps the order in which the
 // cursors were served.
 //
@@ -17,7 +17,7 @@
 //
 // An index outside [0, N) is never dereferenced: its edge length is NaN, its Laplacian row is NaN, and in the
 // backwards its row takes no part in the scatter while its centre point's gradient is NaN.
-#include "pp_common.h"
+#include "bucket_lists.h"
 
 namespace {
 
@@ -26,27 +26,6 @@ constexpr int kKeMaxD = 32;
 constexpr int kKeThreads = 256;
 constexpr int kKeRows = 64;        // rows of idx per workgroup in the tiled kernels
 constexpr int kKeTileK = 32;       // neighbours per row staged at a time by the Laplacian forward
-constexpr int kKeLongRow = 256;    // incoming lists beyond this are sorted by a whole workgroup
-constexpr int kKeSortThreads = 1024;
-constexpr int kKeSortBlocks = 256;
-
-struct KeLayout {
-  size_t nlong, cursor, start, longlist, entries, total;
-};
-__host__ __device__ inline size_t ke_align(size_t x) { return (x + 255) & ~(size_t)255; }
-__host__ __device__ inline KeLayout ke_layout(int B, int N, int K) {
-  const size_t rows = (size_t)B * N, edges = rows * K;
-  KeLayout L;
-  L.nlong = 0;                                  // one counter; zeroed together with the cursors behind it
-  L.cursor = 256;                               // u32 [B*N]: in-degree, then fill cursor, finally the list's end
-  L.start = L.cursor + ke_align(4 * rows);      // u32 [B*N]: the list's first entry (within the batch element)
-  L.longlist = L.start + ke_align(4 * rows);    // u32 [edges / kKeLongRow + 1]: destinations with a long list
-  L.entries = L.longlist + ke_align(4 * (edges / kKeLongRow + 1));
-  L.total = L.entries + ke_align(4 * edges);    // u32 [B][N*K]: edge numbers n*K+k, grouped by destination
-  return L;
-}
-
-__device__ __forceinline__ float ke_nan() { return __int_as_float(0x7fc00000); }
 
 // ---- forwards ---------------------------------------------------------------------------------------------------
 // one thread per edge
@@ -61,7 +40,7 @@ __global__ __launch_bounds__(kKeThreads) void ke_len_forward_kernel(const float*
   const long long row = e / K;
   const long long j = idx[e];
   if (j < 0 || j >= N) {
-    out[e] = ke_nan();
+    out[e] = pp::quiet_nan();
     return;
   }
   const float* __restrict__ pc = points + (size_t)row * Dd;
@@ -134,7 +113,7 @@ __global__ __launch_bounds__(kKeThreads) void ke_lap_forward_kernel(const float*
     if (item < items) {
       const size_t o = (size_t)r0 * Dd + item;
       const float m = -(acc[u] / kf);
-      lap[o] = ((bad >> u) & 1u) ? ke_nan() : m + points[o];
+      lap[o] = ((bad >> u) & 1u) ? pp::quiet_nan() : m + points[o];
     }
   }
 }
@@ -165,101 +144,8 @@ __global__ __launch_bounds__(kKeThreads) void ke_adjacency_kernel(const long lon
     const long long row = r0 + r;
     const long long b = row / N;
     const int n = (int)(row - b * N);
-    unsigned* cur = cursor + (size_t)b * N + (size_t)tile[e];
-    if (!FILL) {
-      atomicAdd(cur, 1u);
-    } else {
-      const unsigned pos = atomicAdd(cur, 1u);   // < N*K: a batch element has no more valid edges than that
-      entries[(size_t)b * N * K + pos] = (unsigned)n * (unsigned)K + (unsigned)(e - r * K);
-    }
-  }
-}
-
-// one workgroup per batch element: exclusive scan of the in-degrees -> start, cursor
-__global__ __launch_bounds__(1024) void ke_scan_kernel(unsigned* __restrict__ cursor, unsigned* __restrict__ start,
-                                                       int N) {
-  __shared__ unsigned s_wave[16];
-  __shared__ unsigned s_carry;
-  const int t = threadIdx.x;
-  unsigned* cur = cursor + (size_t)blockIdx.x * N;
-  unsigned* st = start + (size_t)blockIdx.x * N;
-  if (t == 0) s_carry = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < N; i0 += 1024) {
-    const int i = i0 + t;
-    const unsigned v = i < N ? cur[i] : 0u;
-    unsigned incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned o = __shfl_up(incl, off);
-      if ((t & 63) >= off) incl += o;
-    }
-    if ((t & 63) == 63) s_wave[t >> 6] = incl;
-    __syncthreads();
-    unsigned run = s_carry + incl - v;
-    for (int w = 0; w < (t >> 6); ++w) run += s_wave[w];
-    if (i < N) {
-      st[i] = run;
-      cur[i] = run;
-    }
-    __syncthreads();
-    if (t == 1023) s_carry = run + v;
-  }
-}
-
-// ORDERED: one lane per destination sorts its list by edge number (pp::lane_sort); a list beyond kKeLongRow entries
-// is left to ke_sort_long_kernel
-__global__ __launch_bounds__(kKeThreads) void ke_sort_kernel(const unsigned* __restrict__ start,
-                                                             const unsigned* __restrict__ cursor,
-                                                             unsigned* __restrict__ entries,
-                                                             unsigned* __restrict__ nlong,
-                                                             unsigned* __restrict__ longlist, long long rows, int N,
-                                                             int K) {
-  const long long i = (long long)blockIdx.x * kKeThreads + threadIdx.x;
-  if (i >= rows) return;
-  const unsigned s = start[i], n = cursor[i] - s;
-  if (n > (unsigned)kKeLongRow) {
-    longlist[atomicAdd(nlong, 1u)] = (unsigned)i;   // rows < 2^32 is checked by the host
-    return;
-  }
-  unsigned* grp = entries + (size_t)(i / N) * N * K + s;
-  pp::lane_sort(
-      n, [&](unsigned a) { return grp[a]; },
-      [&](unsigned a, unsigned b) {
-        const unsigned e = grp[a];
-        grp[a] = grp[b];
-        grp[b] = e;
-      });
-}
-
-// ORDERED: a workgroup per long list, bitonic network in place with every comparison ascending (the first step of a
-// merge pairs i with its mirror image in the block), so that a list of any length sorts as if padded with +inf
-__global__ __launch_bounds__(kKeSortThreads) void ke_sort_long_kernel(const unsigned* __restrict__ start,
-                                                                      const unsigned* __restrict__ cursor,
-                                                                      unsigned* entries, const unsigned* nlong,
-                                                                      const unsigned* longlist, int N, int K) {
-  const unsigned count = *nlong;
-  for (unsigned q = blockIdx.x; q < count; q += gridDim.x) {
-    const unsigned i = longlist[q];
-    const unsigned s = start[i], n = cursor[i] - s;
-    unsigned* grp = entries + (size_t)(i / (unsigned)N) * N * K + s;
-    auto pass = [&](unsigned mask) {
-      for (unsigned a = threadIdx.x; a < n; a += kKeSortThreads) {
-        const unsigned b = a ^ mask;
-        if (b > a && b < n) {
-          const unsigned x = grp[a], y = grp[b];
-          if (x > y) {
-            grp[a] = y;
-            grp[b] = x;
-          }
-        }
-      }
-      __syncthreads();
-    };
-    for (unsigned k = 2; (k >> 1) < n; k <<= 1) {
-      pass(k - 1);
-      for (unsigned j = k >> 2; j > 0; j >>= 1) pass(j);
-    }
+    pp::bucket_put<FILL>(cursor, entries, b, N, (long long)N * K, (size_t)tile[e],
+                         (unsigned)n * (unsigned)K + (unsigned)(e - r * K));
   }
 }
 
@@ -333,7 +219,7 @@ __global__ __launch_bounds__(kKeThreads) void ke_len_backward_kernel(
     }
   }
 #pragma unroll
-  for (int c = 0; c < NC; ++c) grad[(size_t)i * Dd + c0 + c] = bad ? ke_nan() : acc[c].s;
+  for (int c = 0; c < NC; ++c) grad[(size_t)i * Dd + c0 + c] = bad ? pp::quiet_nan() : acc[c].s;
 }
 
 template <int DS>
@@ -365,7 +251,7 @@ __global__ __launch_bounds__(kKeThreads) void ke_lap_backward_kernel(
     for (int c = 0; c < NC; ++c) acc[c].add(-(gb[(size_t)n * Dd + c] / kf), ordered);
   }
 #pragma unroll
-  for (int c = 0; c < NC; ++c) grad[(size_t)i * Dd + c0 + c] = bad ? ke_nan() : acc[c].s;
+  for (int c = 0; c < NC; ++c) grad[(size_t)i * Dd + c0 + c] = bad ? pp::quiet_nan() : acc[c].s;
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------
@@ -376,41 +262,26 @@ bool ke_shape_ok(int B, int N, int K, int D) {
          ((long long)B * N * K + kKeThreads - 1) / kKeThreads <= 0x7fffffffLL;
 }
 
-unsigned ke_blocks(long long work, int per_block) { return (unsigned)((work + per_block - 1) / per_block); }
-
-int ke_build_adjacency(const long long* idx, unsigned char* ws, int B, int N, int K, int ordered, hipStream_t s) {
-  const KeLayout L = ke_layout(B, N, K);
+// the reverse adjacency (bucket_lists.h): the edge numbers n*K+k of a batch element, bucketed by destination point
+int ke_build_adjacency(const long long* idx, unsigned char* ws, const pp::BucketLayout& L, int B, int N, int K,
+                       int ordered, hipStream_t s) {
   const long long rows = (long long)B * N;
-  unsigned* nlong = reinterpret_cast<unsigned*>(ws + L.nlong);
   unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
-  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
-  unsigned* longlist = reinterpret_cast<unsigned*>(ws + L.longlist);
   unsigned* entries = reinterpret_cast<unsigned*>(ws + L.entries);
-  const hipError_t e = pp::fill_bytes(ws, 0, L.start, s);   // the counter and the in-degrees
-  if (e != hipSuccess) return (int)e;
-  const unsigned tiles = ke_blocks(rows, kKeRows);
-  ke_adjacency_kernel<false><<<dim3(tiles), dim3(kKeThreads), 0, s>>>(idx, cursor, entries, rows, N, K);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  ke_scan_kernel<<<dim3((unsigned)B), dim3(1024), 0, s>>>(cursor, start, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  ke_adjacency_kernel<true><<<dim3(tiles), dim3(kKeThreads), 0, s>>>(idx, cursor, entries, rows, N, K);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  if (ordered) {
-    ke_sort_kernel<<<dim3(ke_blocks(rows, kKeThreads)), dim3(kKeThreads), 0, s>>>(start, cursor, entries, nlong,
-                                                                                   longlist, rows, N, K);
-    PP_RETURN_IF_LAUNCH_FAILED();
-    ke_sort_long_kernel<<<dim3(kKeSortBlocks), dim3(kKeSortThreads), 0, s>>>(start, cursor, entries, nlong, longlist,
-                                                                             N, K);
-    PP_RETURN_IF_LAUNCH_FAILED();
-  }
-  return PP_OK;
+  return pp::bucket_build(ws, L, entries, nullptr, B, N, (long long)N * K, ordered != 0, s, [&](bool fill) {
+    const dim3 grid(pp::blocks(rows, kKeRows)), block(kKeThreads);
+    if (fill)
+      ke_adjacency_kernel<true><<<grid, block, 0, s>>>(idx, cursor, entries, rows, N, K);
+    else
+      ke_adjacency_kernel<false><<<grid, block, 0, s>>>(idx, cursor, entries, rows, N, K);
+  });
 }
 
 }  // namespace
 
 extern "C" size_t pp_knn_edges_workspace_bytes(int B, int N, int K) {
   if (B <= 0 || N <= 0 || !ke_shape_ok(B, N, K, 1)) return 0;
-  return ke_layout(B, N, K).total;
+  return pp::bucket_layout(B, N, (long long)N * K, false).total;
 }
 
 extern "C" int pp_knn_edge_lengths_forward_f32(const float* points, const long long* idx, float* out, int B, int N,
@@ -421,10 +292,10 @@ extern "C" int pp_knn_edge_lengths_forward_f32(const float* points, const long l
   const long long edges = (long long)B * N * K;
   hipStream_t s = (hipStream_t)stream;
   if (D == 3)
-    ke_len_forward_kernel<3><<<dim3(ke_blocks(edges, kKeThreads)), dim3(kKeThreads), 0, s>>>(points, idx, out, edges,
+    ke_len_forward_kernel<3><<<dim3(pp::blocks(edges, kKeThreads)), dim3(kKeThreads), 0, s>>>(points, idx, out, edges,
                                                                                              N, K, D, squared);
   else
-    ke_len_forward_kernel<0><<<dim3(ke_blocks(edges, kKeThreads)), dim3(kKeThreads), 0, s>>>(points, idx, out, edges,
+    ke_len_forward_kernel<0><<<dim3(pp::blocks(edges, kKeThreads)), dim3(kKeThreads), 0, s>>>(points, idx, out, edges,
                                                                                              N, K, D, squared);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -437,12 +308,12 @@ extern "C" int pp_knn_edge_lengths_backward_f32(const float* points, const long 
   if (!ke_shape_ok(B, N, K, D)) return PP_EINVAL;
   if (B == 0 || N == 0) return PP_OK;
   if (!points || !idx || !out || !grad_out || !grad_points) return PP_EINVAL;
-  const KeLayout L = ke_layout(B, N, K);
+  const pp::BucketLayout L = pp::bucket_layout(B, N, (long long)N * K, false);
   unsigned char* ws = (unsigned char*)workspace;
   if (!detach_neighbors && (!ws || workspace_bytes < L.total)) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (!detach_neighbors) {
-    const int rc = ke_build_adjacency(idx, ws, B, N, K, ordered, s);
+    const int rc = ke_build_adjacency(idx, ws, L, B, N, K, ordered, s);
     if (rc != PP_OK) return rc;
   }
   const unsigned* start = detach_neighbors ? nullptr : reinterpret_cast<const unsigned*>(ws + L.start);
@@ -450,10 +321,10 @@ extern "C" int pp_knn_edge_lengths_backward_f32(const float* points, const long 
   const unsigned* entries = detach_neighbors ? nullptr : reinterpret_cast<const unsigned*>(ws + L.entries);
   const long long rows = (long long)B * N;
   if (D == 3)
-    ke_len_backward_kernel<3><<<dim3(ke_blocks(rows, kKeThreads)), dim3(kKeThreads), 0, s>>>(
+    ke_len_backward_kernel<3><<<dim3(pp::blocks(rows, kKeThreads)), dim3(kKeThreads), 0, s>>>(
         points, idx, out, grad_out, grad_points, start, cursor, entries, rows, N, K, D, squared, detach_neighbors, ordered);
   else
-    ke_len_backward_kernel<0><<<dim3(ke_blocks(rows * D, kKeThreads)), dim3(kKeThreads), 0, s>>>(
+    ke_len_backward_kernel<0><<<dim3(pp::blocks(rows * D, kKeThreads)), dim3(kKeThreads), 0, s>>>(
         points, idx, out, grad_out, grad_points, start, cursor, entries, rows, N, K, D, squared, detach_neighbors, ordered);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -467,9 +338,9 @@ extern "C" int pp_knn_laplacian_forward_f32(const float* points, const long long
   const long long rows = (long long)B * N;
   hipStream_t s = (hipStream_t)stream;
   if (D == 3)
-    ke_lap_forward_kernel<3><<<dim3(ke_blocks(rows, kKeRows)), dim3(kKeThreads), 0, s>>>(points, idx, lap, rows, N, K, D);
+    ke_lap_forward_kernel<3><<<dim3(pp::blocks(rows, kKeRows)), dim3(kKeThreads), 0, s>>>(points, idx, lap, rows, N, K, D);
   else
-    ke_lap_forward_kernel<0><<<dim3(ke_blocks(rows, kKeRows)), dim3(kKeThreads), 0, s>>>(points, idx, lap, rows, N, K, D);
+    ke_lap_forward_kernel<0><<<dim3(pp::blocks(rows, kKeRows)), dim3(kKeThreads), 0, s>>>(points, idx, lap, rows, N, K, D);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }
@@ -480,21 +351,21 @@ extern "C" int pp_knn_laplacian_backward_f32(const long long* idx, const float* 
   if (!ke_shape_ok(B, N, K, D)) return PP_EINVAL;
   if (B == 0 || N == 0) return PP_OK;
   if (!idx || !grad_lap || !grad_points) return PP_EINVAL;
-  const KeLayout L = ke_layout(B, N, K);
+  const pp::BucketLayout L = pp::bucket_layout(B, N, (long long)N * K, false);
   unsigned char* ws = (unsigned char*)workspace;
   if (!ws || workspace_bytes < L.total) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const int rc = ke_build_adjacency(idx, ws, B, N, K, ordered, s);
+  const int rc = ke_build_adjacency(idx, ws, L, B, N, K, ordered, s);
   if (rc != PP_OK) return rc;
   const unsigned* start = reinterpret_cast<const unsigned*>(ws + L.start);
   const unsigned* cursor = reinterpret_cast<const unsigned*>(ws + L.cursor);
   const unsigned* entries = reinterpret_cast<const unsigned*>(ws + L.entries);
   const long long rows = (long long)B * N;
   if (D == 3)
-    ke_lap_backward_kernel<3><<<dim3(ke_blocks(rows, kKeThreads)), dim3(kKeThreads), 0, s>>>(
+    ke_lap_backward_kernel<3><<<dim3(pp::blocks(rows, kKeThreads)), dim3(kKeThreads), 0, s>>>(
         idx, grad_lap, grad_points, start, cursor, entries, rows, N, K, D, ordered);
   else
-    ke_lap_backward_kernel<0><<<dim3(ke_blocks(rows * D, kKeThreads)), dim3(kKeThreads), 0, s>>>(
+    ke_lap_backward_kernel<0><<<dim3(pp::blocks(rows * D, kKeThreads)), dim3(kKeThreads), 0, s>>>(
         idx, grad_lap, grad_points, start, cursor, entries, rows, N, K, D, ordered);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;

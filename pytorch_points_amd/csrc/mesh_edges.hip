@@ -6,13 +6,13 @@
 // Here the topology is built ONCE and kept (a mesh's connectivity does not change between training steps):
 //   unique edges   faces (Bt,F,3) -> edges (Bt,3F,2): the unordered vertex pairs as (min,max), ascending
 //                  lexicographically, rows from count[b] on (-1,-1); row for row what torch.unique(dim=0) of the sorted
-//                  half-edges returns.  Half-edges are bucketed by their min-vertex (integer atomics, a scan per batch
-//                  element, a fill through integer cursors), every bucket is SORTED by max-vertex, the first entry of
-//                  every run of equal pairs is ranked by a second scan and written compacted.  The sort makes the
-//                  result independent of the order in which the atomics were served.
+//                  half-edges returns.  Half-edges are bucketed by their min-vertex and every bucket is SORTED by
+//                  max-vertex (bucket_lists.h's chain), the first entry of every run of equal pairs is ranked by a
+//                  second scan and written compacted.  The sort makes the result independent of the order in which
+//                  the atomics were served.
 //   incidence      edges (Bt,Ecap,2), counts -> for every vertex the list of 2*e + side over the edges e < count[b]
-//                  with edges[e,side] == v, ascending (the same bucket / scan / fill / sort chain).  The edge list may
-//                  be any list: not unique, not sorted, with self-edges.
+//                  with edges[e,side] == v, ascending (the same chain).  The edge list may be any list: not unique,
+//                  not sorted, with self-edges.
 // and a training step is two launches:
 //   forward        out[b,e] = |v[b,edges[e,0]] - v[b,edges[e,1]]|^2 (pp::chamfer_d3: the bits of knn_edge_lengths'
 //                  squared form), one thread per edge; 0 for the padding rows
@@ -32,35 +32,12 @@
 //   apply              one thread per (b, vertex): a gather over the vertex's slice from +0 in slot order, plain fp32
 //                      operations; the uniform operator's forward and backward and the cotangent operator (whose
 //                      backward is the same call on the gradient) are three modes of one kernel
-#include "pp_common.h"
+#include "bucket_lists.h"
 
 namespace {
 
 constexpr int kMeThreads = 256;
-constexpr int kMeLongList = 256;    // buckets beyond this are sorted by a whole workgroup
-constexpr int kMeSortThreads = 1024;
-constexpr int kMeSortBlocks = 256;
-constexpr int kMeScanThreads = 1024;
-
-// scratch of one build: `items` entries per batch element (3F half-edges, or 2*Ecap edge ends) over N vertices
-struct MeLayout {
-  size_t nlong, cursor, start, longlist, entries, owner, total;
-};
-__host__ __device__ inline size_t me_align(size_t x) { return (x + 255) & ~(size_t)255; }
-__host__ __device__ inline MeLayout me_layout(int Bt, int N, long long items) {
-  const size_t rows = (size_t)Bt * N, all = (size_t)Bt * (size_t)items;
-  MeLayout L;
-  L.nlong = 0;                                 // one counter; zeroed together with the cursors behind it
-  L.cursor = 256;                              // u32 [Bt*N]: bucket size, then fill cursor, finally the bucket's end
-  L.start = L.cursor + me_align(4 * rows);     // u32 [Bt*N]: the bucket's first entry (within the batch element)
-  L.longlist = L.start + me_align(4 * rows);   // u32 [all / kMeLongList + 1]: buckets with a long list
-  L.entries = L.longlist + me_align(4 * (all / kMeLongList + 1));
-  L.owner = L.entries + me_align(4 * all);     // u32 [Bt][items]: the bucket of every entry (unique edges only)
-  L.total = L.owner + me_align(4 * all);
-  return L;
-}
-
-__device__ __forceinline__ float me_nan() { return __int_as_float(0x7fc00000); }
+constexpr int kMeScanThreads = pp::kBucketScanThreads;   // me_compact_kernel ranks with the chain's block scan
 
 // ---- buckets ------------------------------------------------------------------------------------------------------
 // Half-edge j of face f joins corners j and (j+1) mod 3.  FILL = false: bucket sizes by min-vertex; FILL = true: the
@@ -85,14 +62,8 @@ __global__ __launch_bounds__(kMeThreads) void me_half_edges_kernel(const long lo
     return;
   }
   const unsigned mn = (unsigned)(p < q ? p : q), mx = (unsigned)(p < q ? q : p);
-  unsigned* cur = cursor + (size_t)b * N + mn;
-  if (!FILL) {
-    atomicAdd(cur, 1u);
-  } else {
-    const unsigned pos = atomicAdd(cur, 1u);   // < 3F: a batch element has no more valid half-edges than that
-    entries[(size_t)b * H + pos] = mx;
-    owner[(size_t)b * H + pos] = mn;
-  }
+  const size_t slot = pp::bucket_put<FILL>(cursor, entries, b, N, H, mn, mx);
+  if (FILL) owner[slot] = mn;
 }
 
 // One thread per edge end (b, e, side), e < counts[b].  FILL = false: the vertices' degrees; FILL = true: the lists
@@ -115,119 +86,7 @@ __global__ __launch_bounds__(kMeThreads) void me_edge_ends_kernel(const long lon
     if (!FILL) atomicOr(flags + b, 1);
     return;
   }
-  unsigned* cur = cursor + (size_t)b * N + (size_t)v;
-  if (!FILL) {
-    atomicAdd(cur, 1u);
-  } else {
-    const unsigned pos = atomicAdd(cur, 1u);   // < 2*Ecap
-    entries[(size_t)b * X + pos] = code;
-  }
-}
-
-// exclusive scan of one chunk of kMeScanThreads values inside a workgroup; returns the value's exclusive prefix
-// including `carry`, and leaves the chunk's total in *chunk_total (valid after the call for every thread)
-__device__ __forceinline__ unsigned me_block_scan(unsigned v, unsigned carry, unsigned* s_wave, unsigned* chunk_total) {
-  const int t = threadIdx.x;
-  unsigned incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned o = __shfl_up(incl, off);
-    if ((t & 63) >= off) incl += o;
-  }
-  __syncthreads();   // the previous chunk's readers of s_wave are done
-  if ((t & 63) == 63) s_wave[t >> 6] = incl;
-  __syncthreads();
-  unsigned run = carry + incl - v, all = 0;
-  for (int w = 0; w < kMeScanThreads / 64; ++w) {
-    const unsigned s = s_wave[w];
-    if (w < (t >> 6)) run += s;
-    all += s;
-  }
-  *chunk_total = all;
-  return run;
-}
-
-// one workgroup per batch element: exclusive scan of the bucket sizes -> start, cursor; start2 (nullable, stride N+1,
-// the incidence's public form) receives the same values and the total behind them
-__global__ __launch_bounds__(kMeScanThreads) void me_scan_kernel(unsigned* __restrict__ cursor,
-                                                                 unsigned* __restrict__ start,
-                                                                 int* __restrict__ start2, int N) {
-  __shared__ unsigned s_wave[kMeScanThreads / 64];
-  const int t = threadIdx.x;
-  unsigned* cur = cursor + (size_t)blockIdx.x * N;
-  unsigned* st = start + (size_t)blockIdx.x * N;
-  int* st2 = start2 ? start2 + (size_t)blockIdx.x * ((size_t)N + 1) : nullptr;
-  unsigned carry = 0;
-  for (int i0 = 0; i0 < N; i0 += kMeScanThreads) {
-    const int i = i0 + t;
-    const unsigned v = i < N ? cur[i] : 0u;
-    unsigned chunk;
-    const unsigned run = me_block_scan(v, carry, s_wave, &chunk);
-    if (i < N) {
-      st[i] = run;
-      cur[i] = run;
-      if (st2) st2[i] = (int)run;
-    }
-    carry += chunk;
-  }
-  if (st2 && t == 0) st2[N] = (int)carry;
-}
-
-// one lane per bucket sorts it ascending (pp::lane_sort); a bucket beyond kMeLongList entries is left to
-// me_sort_long_kernel.  Equal keys (a pair that several faces share) need no order among themselves.
-__global__ __launch_bounds__(kMeThreads) void me_sort_kernel(const unsigned* __restrict__ start,
-                                                             const unsigned* __restrict__ cursor,
-                                                             unsigned* __restrict__ entries,
-                                                             unsigned* __restrict__ nlong,
-                                                             unsigned* __restrict__ longlist, long long rows, int N,
-                                                             long long items) {
-  const long long i = (long long)blockIdx.x * kMeThreads + threadIdx.x;
-  if (i >= rows) return;
-  const unsigned s = start[i], n = cursor[i] - s;
-  if (n > (unsigned)kMeLongList) {
-    longlist[atomicAdd(nlong, 1u)] = (unsigned)i;   // rows < 2^31 is checked by the host; at most all/256 long buckets
-    return;
-  }
-  unsigned* grp = entries + (size_t)(i / N) * (size_t)items + s;
-  pp::lane_sort(
-      n, [&](unsigned a) { return grp[a]; },
-      [&](unsigned a, unsigned b) {
-        const unsigned e = grp[a];
-        grp[a] = grp[b];
-        grp[b] = e;
-      });
-}
-
-// a workgroup per long bucket: bitonic network in place with every comparison ascending (the first step of a merge
-// pairs i with its mirror image in the block), so that a list of any length sorts as if padded with +inf
-__global__ __launch_bounds__(kMeSortThreads) void me_sort_long_kernel(const unsigned* __restrict__ start,
-                                                                      const unsigned* __restrict__ cursor,
-                                                                      unsigned* entries, const unsigned* nlong,
-                                                                      const unsigned* longlist, int N,
-                                                                      long long items) {
-  const unsigned count = *nlong;
-  for (unsigned q = blockIdx.x; q < count; q += gridDim.x) {
-    const unsigned i = longlist[q];
-    const unsigned s = start[i], n = cursor[i] - s;
-    unsigned* grp = entries + (size_t)(i / (unsigned)N) * (size_t)items + s;
-    auto pass = [&](unsigned mask) {
-      for (unsigned a = threadIdx.x; a < n; a += kMeSortThreads) {
-        const unsigned b = a ^ mask;
-        if (b > a && b < n) {
-          const unsigned x = grp[a], y = grp[b];
-          if (x > y) {
-            grp[a] = y;
-            grp[b] = x;
-          }
-        }
-      }
-      __syncthreads();
-    };
-    for (unsigned k = 2; (k >> 1) < n; k <<= 1) {
-      pass(k - 1);
-      for (unsigned j = k >> 2; j > 0; j >>= 1) pass(j);
-    }
-  }
+  pp::bucket_put<FILL>(cursor, entries, b, N, X, (size_t)v, code);
 }
 
 // one workgroup per batch element over its sorted (owner, entry) pairs: a position that differs from the one before it
@@ -254,7 +113,7 @@ __global__ __launch_bounds__(kMeScanThreads) void me_compact_kernel(const unsign
       first = (q == 0 || own[q - 1] != mn || ent[q - 1] != mx) ? 1u : 0u;
     }
     unsigned chunk;
-    const unsigned rank = me_block_scan(first, carry, s_wave, &chunk);
+    const unsigned rank = pp::bucket_block_scan(first, carry, s_wave, &chunk);
     if (first) {
       out[2 * (size_t)rank] = (long long)mn;
       out[2 * (size_t)rank + 1] = (long long)mx;
@@ -283,7 +142,7 @@ __global__ __launch_bounds__(kMeThreads) void me_sqrlen_forward_kernel(const flo
   }
   const long long a = edges[(tb * Ecap + e) * 2], c = edges[(tb * Ecap + e) * 2 + 1];
   if (a < 0 || a >= N || c < 0 || c >= N) {
-    out[x] = me_nan();
+    out[x] = pp::quiet_nan();
     return;
   }
   const float* __restrict__ pa = vertices + ((size_t)b * N + (size_t)a) * 3;
@@ -315,7 +174,7 @@ __global__ __launch_bounds__(kMeThreads) void me_sqrlen_backward_kernel(
     const float coef = 2.0f * gb[e];
     float tx, ty, tz;
     if (o < 0 || o >= N) {
-      tx = ty = tz = me_nan();
+      tx = ty = tz = pp::quiet_nan();
     } else {
       const float ox = vb[o * 3], oy = vb[o * 3 + 1], oz = vb[o * 3 + 2];
       // v_a - v_b with a = edges[e,0], b = edges[e,1]
@@ -355,13 +214,7 @@ __global__ __launch_bounds__(kMeThreads) void me_corners_kernel(const long long*
     if (!FILL) atomicOr(flags + b, 1);
     return;
   }
-  unsigned* cur = cursor + (size_t)b * N + (size_t)v;
-  if (!FILL) {
-    atomicAdd(cur, 1u);
-  } else {
-    const unsigned pos = atomicAdd(cur, 1u);   // < L*F
-    entries[(size_t)b * X + pos] = (unsigned)(x - b * X);
-  }
+  pp::bucket_put<FILL>(cursor, entries, b, N, X, (size_t)v, (unsigned)(x - b * X));
 }
 
 // One thread per slot of the sorted lists: (next, prev) of the slot's corner, -1 for a vertex outside [0, N), so that
@@ -399,7 +252,7 @@ __global__ __launch_bounds__(kMeThreads) void me_cotangent_kernel(const float* _
   const long long i1 = row[0], i2 = row[1], i3 = row[2];
   float* __restrict__ o = out + x * 3;
   if (i1 < 0 || i1 >= N || i2 < 0 || i2 >= N || i3 < 0 || i3 >= N) {
-    o[0] = o[1] = o[2] = me_nan();
+    o[0] = o[1] = o[2] = pp::quiet_nan();
     return;
   }
   const float* __restrict__ vb = vertices + (size_t)b * N * 3;
@@ -470,7 +323,7 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
         w[0] = wb[(size_t)f * 3 + (c == 0 ? 2 : c - 1)];   // (c + 2) % 3
         w[1] = wb[(size_t)f * 3 + (c == 2 ? 0 : c + 1)];   // (c + 1) % 3
       } else {
-        w[0] = w[1] = me_nan();
+        w[0] = w[1] = pp::quiet_nan();
       }
     }
 #pragma unroll
@@ -478,7 +331,7 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
       const int j = side ? jk.y : jk.x;
       float ox, oy, oz;
       if (j < 0 || j >= N) {
-        ox = oy = oz = me_nan();
+        ox = oy = oz = pp::quiet_nan();
       } else {
         ox = xb[(size_t)j * 3];
         oy = xb[(size_t)j * 3 + 1];
@@ -518,29 +371,11 @@ bool me_build_ok(int Bt, int N, long long items) {
   return Bt >= 0 && N >= 0 && items >= 0 && (long long)Bt * items <= 0x7fffffffLL && (long long)Bt * N <= 0x7fffffffLL;
 }
 
-unsigned me_blocks(long long work, int per_block) { return (unsigned)((work + per_block - 1) / per_block); }
-
-int me_sort_buckets(unsigned char* ws, const MeLayout& L, unsigned* entries, int Bt, int N, long long items,
-                    hipStream_t s) {
-  const long long rows = (long long)Bt * N;
-  unsigned* nlong = reinterpret_cast<unsigned*>(ws + L.nlong);
-  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
-  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
-  unsigned* longlist = reinterpret_cast<unsigned*>(ws + L.longlist);
-  me_sort_kernel<<<dim3(me_blocks(rows, kMeThreads)), dim3(kMeThreads), 0, s>>>(start, cursor, entries, nlong, longlist,
-                                                                                 rows, N, items);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_sort_long_kernel<<<dim3(kMeSortBlocks), dim3(kMeSortThreads), 0, s>>>(start, cursor, entries, nlong, longlist, N,
-                                                                           items);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
 }  // namespace
 
 extern "C" size_t pp_mesh_edges_workspace_bytes(int Bt, int n_vertices, long long items) {
   if (Bt <= 0 || n_vertices <= 0 || items <= 0 || !me_build_ok(Bt, n_vertices, items)) return 0;
-  return me_layout(Bt, n_vertices, items).total;
+  return pp::bucket_layout(Bt, n_vertices, items, true).total;
 }
 
 extern "C" int pp_mesh_unique_edges(const long long* faces, long long* edges, int* counts, int* flags, int Bt, int F,
@@ -562,25 +397,20 @@ extern "C" int pp_mesh_unique_edges(const long long* faces, long long* edges, in
     if (e != hipSuccess) return (int)e;
     return (int)pp::fill_bytes(flags, 1, 4 * (size_t)Bt, s);   // (any non-zero word)
   }
-  const MeLayout L = me_layout(Bt, N, H);
+  const pp::BucketLayout L = pp::bucket_layout(Bt, N, H, true);
   unsigned char* ws = (unsigned char*)workspace;
   if (!faces || !edges || !ws || workspace_bytes < L.total) return PP_EINVAL;
   unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
-  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
   unsigned* entries = reinterpret_cast<unsigned*>(ws + L.entries);
   unsigned* owner = reinterpret_cast<unsigned*>(ws + L.owner);
-  e = pp::fill_bytes(ws, 0, L.start, s);   // the counter and the bucket sizes
-  if (e != hipSuccess) return (int)e;
   const long long total = (long long)Bt * H;
-  me_half_edges_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, entries,
-                                                                                               owner, flags, total, F, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_scan_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, start, nullptr, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_half_edges_kernel<true><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, entries,
-                                                                                              owner, flags, total, F, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  const int rc = me_sort_buckets(ws, L, entries, Bt, N, H, s);
+  const int rc = pp::bucket_build(ws, L, entries, nullptr, Bt, N, H, true, s, [&](bool fill) {
+    const dim3 grid(pp::blocks(total, kMeThreads)), block(kMeThreads);
+    if (fill)
+      me_half_edges_kernel<true><<<grid, block, 0, s>>>(faces, cursor, entries, owner, flags, total, F, N);
+    else
+      me_half_edges_kernel<false><<<grid, block, 0, s>>>(faces, cursor, entries, owner, flags, total, F, N);
+  });
   if (rc != PP_OK) return rc;
   me_compact_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, entries, owner, edges, counts, N, F);
   PP_RETURN_IF_LAUNCH_FAILED();
@@ -604,28 +434,22 @@ extern "C" int pp_mesh_edge_incidence(const long long* edges, const int* counts,
   if (!edges || !counts || !flags) return PP_EINVAL;
   const long long total = (long long)Bt * X;
   if (N == 0) {   // every end of every counted edge is out of range: the count pass only compares and flags
-    me_edge_ends_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(
+    me_edge_ends_kernel<false><<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(
         edges, counts, nullptr, nullptr, flags, total, Ecap, N);
     PP_RETURN_IF_LAUNCH_FAILED();
     return PP_OK;
   }
-  const MeLayout L = me_layout(Bt, N, X);
+  const pp::BucketLayout L = pp::bucket_layout(Bt, N, X, false);
   unsigned char* ws = (unsigned char*)workspace;
   if (!inc_entries || !ws || workspace_bytes < L.entries) return PP_EINVAL;   // the lists are built in place
   unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
-  unsigned* start = reinterpret_cast<unsigned*>(ws + L.start);
-  unsigned* entries = inc_entries;
-  hipError_t e = pp::fill_bytes(ws, 0, L.start, s);
-  if (e != hipSuccess) return (int)e;
-  me_edge_ends_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(edges, counts, cursor,
-                                                                                              entries, flags, total, Ecap, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_scan_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, start, inc_start, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_edge_ends_kernel<true><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(edges, counts, cursor,
-                                                                                             entries, flags, total, Ecap, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return me_sort_buckets(ws, L, entries, Bt, N, X, s);
+  return pp::bucket_build(ws, L, inc_entries, inc_start, Bt, N, X, true, s, [&](bool fill) {
+    const dim3 grid(pp::blocks(total, kMeThreads)), block(kMeThreads);
+    if (fill)
+      me_edge_ends_kernel<true><<<grid, block, 0, s>>>(edges, counts, cursor, inc_entries, flags, total, Ecap, N);
+    else
+      me_edge_ends_kernel<false><<<grid, block, 0, s>>>(edges, counts, cursor, inc_entries, flags, total, Ecap, N);
+  });
 }
 
 extern "C" int pp_mesh_edge_sqrlen_forward_f32(const float* vertices, const long long* edges, const int* counts,
@@ -636,7 +460,7 @@ extern "C" int pp_mesh_edge_sqrlen_forward_f32(const float* vertices, const long
   if (B == 0 || Ecap == 0) return PP_OK;
   if (!edges || !counts || !out || (N > 0 && !vertices)) return PP_EINVAL;
   const long long total = (long long)B * Ecap;
-  me_sqrlen_forward_kernel<<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
+  me_sqrlen_forward_kernel<<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
       vertices, edges, counts, out, total, N, Ecap, shared_topology != 0);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -650,7 +474,7 @@ extern "C" int pp_mesh_edge_sqrlen_backward_f32(const float* vertices, const lon
   if (B == 0 || N == 0) return PP_OK;
   if (!vertices || !inc_start || !grad_vertices || (Ecap > 0 && (!edges || !inc_entries || !grad_out))) return PP_EINVAL;
   const long long rows = (long long)B * N;
-  me_sqrlen_backward_kernel<<<dim3(me_blocks(rows, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
+  me_sqrlen_backward_kernel<<<dim3(pp::blocks(rows, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
       vertices, edges, inc_start, inc_entries, grad_out, grad_vertices, rows, N, Ecap, shared_topology != 0);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -674,25 +498,20 @@ extern "C" int pp_mesh_corner_incidence(const long long* faces, int* start, unsi
     if (F == 0) return PP_OK;
     return (int)pp::fill_bytes(flags, 1, 4 * (size_t)Bt, s);   // (any non-zero word)
   }
-  const MeLayout lay = me_layout(Bt, N, X);
+  const pp::BucketLayout lay = pp::bucket_layout(Bt, N, X, false);
   unsigned char* ws = (unsigned char*)workspace;
   if (!faces || !codes || !nbr || !ws || workspace_bytes < lay.entries) return PP_EINVAL;   // the lists are built in place
   unsigned* cursor = reinterpret_cast<unsigned*>(ws + lay.cursor);
-  unsigned* st = reinterpret_cast<unsigned*>(ws + lay.start);
-  e = pp::fill_bytes(ws, 0, lay.start, s);
-  if (e != hipSuccess) return (int)e;
   const long long total = (long long)Bt * X;
-  me_corners_kernel<false><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, codes, flags,
-                                                                                            total, X, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_scan_kernel<<<dim3((unsigned)Bt), dim3(kMeScanThreads), 0, s>>>(cursor, st, start, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  me_corners_kernel<true><<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, cursor, codes, flags,
-                                                                                           total, X, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  const int rc = me_sort_buckets(ws, lay, codes, Bt, N, X, s);
+  const int rc = pp::bucket_build(ws, lay, codes, start, Bt, N, X, true, s, [&](bool fill) {
+    const dim3 grid(pp::blocks(total, kMeThreads)), block(kMeThreads);
+    if (fill)
+      me_corners_kernel<true><<<grid, block, 0, s>>>(faces, cursor, codes, flags, total, X, N);
+    else
+      me_corners_kernel<false><<<grid, block, 0, s>>>(faces, cursor, codes, flags, total, X, N);
+  });
   if (rc != PP_OK) return rc;
-  me_corner_nbr_kernel<<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, start, codes, nbr, total,
+  me_corner_nbr_kernel<<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, start, codes, nbr, total,
                                                                                         X, L, N);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -704,7 +523,7 @@ extern "C" int pp_mesh_cotangent_f32(const float* vertices, const long long* fac
   if (B == 0 || F == 0) return PP_OK;
   if (!faces || !out || (N > 0 && !vertices)) return PP_EINVAL;
   const long long total = (long long)B * F;
-  me_cotangent_kernel<<<dim3(me_blocks(total, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
+  me_cotangent_kernel<<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, (hipStream_t)stream>>>(
       vertices, faces, out, total, N, F, shared_topology != 0);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -719,7 +538,7 @@ extern "C" int pp_mesh_laplacian_apply_f32(const float* x, const int* start, con
   if (B == 0 || N == 0) return PP_OK;
   if (!x || !start || !out || (F > 0 && (!nbr || !codes || (mode == 2 && !weights)))) return PP_EINVAL;
   const long long rows = (long long)B * N;
-  const dim3 grid(me_blocks(rows, kMeThreads)), block(kMeThreads);
+  const dim3 grid(pp::blocks(rows, kMeThreads)), block(kMeThreads);
   hipStream_t s = (hipStream_t)stream;
   const int sh = shared_topology != 0;
   if (mode == 0)

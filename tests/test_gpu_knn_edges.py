@@ -134,9 +134,17 @@ def odd_graph():
     return p, idx
 
 
+def threshold_graph():
+    """in-degrees 256, 257 and 87: on both sides of the longest list that one lane sorts (256 entries)"""
+    idx = np.full((1, 600, 1), 2, np.int64)
+    idx[0, :256] = 0
+    idx[0, 256:513] = 1
+    return cloud(1, 600), idx
+
+
 def backward_cases():
     cases = [("b%d_n%d_k%d" % (b, n, k), (lambda b=b, n=n, k=k: searched(b, n, k)[:2])) for b, n in SHAPES for k in KS]
-    return cases + [("hub", hub_graph), ("loops_and_duplicates", odd_graph)]
+    return cases + [("hub", hub_graph), ("loops_and_duplicates", odd_graph), ("threshold", threshold_graph)]
 
 
 def operators():
@@ -179,7 +187,7 @@ def test_zero_length_gives_zero_gradient(cuda):
 
 
 ORDERED = [("hub", hub_graph), ("n257", lambda: searched(1, 257, 20)[:2]), ("n5000", lambda: searched(3, 5000, 20)[:2]),
-           ("loops_and_duplicates", odd_graph)]
+           ("loops_and_duplicates", odd_graph), ("threshold", threshold_graph)]
 
 
 @pytest.mark.parametrize("name,make", ORDERED, ids=[c[0] for c in ORDERED])

@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 import torch
 
-from pytorch_points_amd import knn_edges, ops
+from pytorch_points_amd import _lib, knn_edges, ops
 from pytorch_points_amd.network import geo_operations, model_loss
+from test_mesh_edges_host import bucket_scratch_bytes
 
 F32 = np.float32
 EPS = 2.0 ** -23
@@ -150,6 +151,18 @@ def test_validation():
         with pytest.raises(NotImplementedError, match="K <= 128"):
             fn(p, torch.zeros(2, 10, 129, dtype=torch.int64))
         assert fn(p, torch.zeros(2, 10, 128, dtype=torch.int32)).shape[:2] == (2, 10)
+
+
+def test_workspace_bytes_follow_the_layout():
+    """pure host arithmetic, callable without a GPU: N*K entries per batch element and no owner region"""
+    size = _lib.lib().pp_knn_edges_workspace_bytes
+    assert bucket_scratch_bytes(2, 70, 70 * 8, False) == 6656
+    # B*N a multiple of 64 and not, B*N*K on both sides of a multiple of 256
+    for b, n, k in [(2, 70, 8), (1, 64, 4), (3, 85, 1), (1, 257, 20), (3, 5000, 33), (1, 1, 128)]:
+        assert size(b, n, k) == bucket_scratch_bytes(b, n, n * k, False), (b, n, k)
+    for b, n, k in [(0, 70, 8), (2, 0, 8), (-1, 70, 8), (2, -1, 8), (2, 70, 0), (2, 70, 129),
+                    (2, 1 << 30, 1), (1, 1 << 28, 8)]:             # B*N or N*K beyond 2^31 - 1
+        assert size(b, n, k) == 0, (b, n, k)
 
 
 # ------------------------------------------------------------------------------------------------- the losses

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from pytorch_points_amd import mesh_edges, synthetic
+from pytorch_points_amd import _lib, mesh_edges, synthetic
 from pytorch_points_amd.network import geo_operations, model_loss
 
 REDUCTIONS = ["mean", "max", "sum", "none"]
@@ -349,6 +349,29 @@ def test_shape_and_dtype_errors():
         mesh_edges.MeshEdges.from_faces(bad, 25)
     with pytest.raises(IndexError, match="batch element 0"):
         mesh_edges.MeshEdges.from_edges(torch.tensor([[0, 25]]), 25)
+
+
+# ------------------------------------------------------------------------------------------------ 5. workspace
+def bucket_scratch_bytes(b, n, items, owner):
+    """csrc/bucket_lists.h's layout restated (also serves tests/test_knn_edges_host.py): 256-byte-aligned regions, a
+    counter slot, cursor and start of one word per vertex, the long list, the entries and, on request, their owners"""
+    def align(x):
+        return (x + 255) // 256 * 256
+    words = [b * n, b * n, b * items // 256 + 1, b * items] + ([b * items] if owner else [])
+    return 256 + sum(align(4 * w) for w in words)
+
+
+def test_workspace_bytes_follow_the_layout():
+    """pure host arithmetic, callable without a GPU"""
+    size = _lib.lib().pp_mesh_edges_workspace_bytes
+    assert bucket_scratch_bytes(1, 257, 9000, True) == 75264
+    # B*N a multiple of 64 and not, items on both sides of a multiple of 256, several batch elements
+    for b, n, items in [(1, 257, 9000), (1, 64, 256), (3, 70, 255), (2, 4, 12), (5, 1, 3), (4, 5000, 30000)]:
+        assert size(b, n, items) == bucket_scratch_bytes(b, n, items, True), (b, n, items)
+    for b, n, items in [(0, 10, 30), (2, 0, 30), (2, 10, 0), (-1, 10, 30), (2, -1, 30), (2, 10, -3),
+                        (2, 10, 1 << 30), (3, 1 << 30, 30)]:       # B*items or B*N beyond 2^31 - 1
+        assert size(b, n, items) == 0, (b, n, items)
+    assert size(1, 10, (1 << 31) - 1) == bucket_scratch_bytes(1, 10, (1 << 31) - 1, True)
 
 
 def test_drop_in_names_resolve():
