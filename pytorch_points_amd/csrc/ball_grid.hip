@@ -10,8 +10,8 @@
 // large against r).
 //
 // The reference's order (ascending index, cut at nsample) is what makes this more than a range
-// query.  A wave takes 64 centres that are close in space (the build kernel also sorts the centres,
-// along a Morton curve), and
+// query.  A wave takes 64 centres that are close in space (the build, grid_pairs.hip, also sorts the
+// centres, along a Morton curve), and
 //   1. marks the cells of the 64 boxes in an LDS bitmap (one bit per cell: the union),
 //   2. marks the points of those cells in an LDS bitmap indexed by ORIGINAL point index,
 //   3. walks that bitmap in order -- the candidates come out sorted by index for free -- and stages
@@ -22,7 +22,7 @@
 //   5. writes the 64 rows, padded, to the centres' original positions.
 // Sets whose box would exceed 7x7x7 cells (large radius), or whose grid is useless, are left to the
 // scan kernel, launched afterwards for those sets only.
-#include "grid_common.h"
+#include "grid_pairs.h"
 
 namespace pp {
 // sampling.hip: the scan kernel over the batch elements whose grid set says "not usable"
@@ -49,7 +49,6 @@ namespace {
 using pp::GridSet;
 using pp::cell_coord;
 using pp::kGridCells;
-using pp::kBuildThreads;
 
 constexpr int kBqMaxCells = 3;   // cell-box half-extent the grid path accepts
 #ifndef PP_BQ_CAP
@@ -57,48 +56,6 @@ constexpr int kBqMaxCells = 3;   // cell-box half-extent the grid path accepts
 #endif
 constexpr int kBqCap = PP_BQ_CAP;  // candidates staged per pass (16 bytes each)
 constexpr int kBqMaxN = 524288;  // point bitmap <= 64 KiB
-
-struct BqLayout {
-  size_t sets, cell_start, sorted, csorted, total;
-};
-__host__ __device__ inline BqLayout bq_layout(int B, int N, int M) {
-  BqLayout L;
-  L.sets = 0;  // [2B]: cloud sets, then the (unused) sets of the centre sort
-  L.cell_start = ((size_t)64 * 2 * B + 255) / 256 * 256;
-  L.sorted = L.cell_start + ((size_t)4 * (kGridCells + 1) * B + 255) / 256 * 256;
-  L.csorted = L.sorted + ((size_t)16 * B * N + 255) / 256 * 256;
-  L.total = L.csorted + (size_t)16 * B * M;
-  return L;
-}
-
-// workgroups [0, S*B): slab s of the cloud of batch element b into its grid; [S*B, 2*S*B): slab s of
-// the centres of batch element b into Morton order (S = kBuildSlabs)
-template <bool VEC>
-__global__ __launch_bounds__(kBuildThreads) void bq_build_kernel(const float* __restrict__ xyz,
-                                                                 const float* __restrict__ new_xyz,
-                                                                 unsigned char* __restrict__ ws, int B, int N,
-                                                                 int M) {
-  extern __shared__ __attribute__((aligned(16))) unsigned s_cnt[];
-  const BqLayout L = bq_layout(B, N, M);
-  // both sets of a batch element are built on the XCD that will search it (the query kernel's batch ->
-  // XCD mapping): virtual order (batch, cloud | queries, slab)
-  const int V = pp::xcd_virtual_block(blockIdx.x, (2 * B * pp::kBuildSlabs + 7) / 8);
-  if (V >= 2 * B * pp::kBuildSlabs) return;
-  const int slab = V % pp::kBuildSlabs;
-  const int set = ((V / pp::kBuildSlabs) & 1) * B + V / (2 * pp::kBuildSlabs);
-  GridSet* gs = reinterpret_cast<GridSet*>(ws + L.sets) + set;
-  if (set >= B) {
-    const int b = set - B;
-    pp::grid_build_set<true, VEC>(new_xyz + (size_t)b * M * 3, M, gs, nullptr,
-                             reinterpret_cast<pp::f4*>(ws + L.csorted) + (size_t)b * M, nullptr, s_cnt, nullptr,
-                             nullptr, slab, pp::kBuildSlabs);
-    return;
-  }
-  const int b = set;
-  pp::grid_build_set_plain<VEC>(xyz + (size_t)b * N * 3, N, gs,
-                                reinterpret_cast<unsigned*>(ws + L.cell_start) + (size_t)b * (kGridCells + 1),
-                                reinterpret_cast<pp::f4*>(ws + L.sorted) + (size_t)b * N, s_cnt, slab, pp::kBuildSlabs);
-}
 
 // the grid path serves this batch element (otherwise the scan kernel does): the grid exists and the
 // cell box of a centre stays within 7 cells per axis
@@ -119,7 +76,7 @@ __global__ __launch_bounds__(64) void bq_query_kernel(const float* __restrict__ 
   if (vb >= B * tiles_per_b) return;
   const int b = vb / tiles_per_b;
   const int tile = vb - b * tiles_per_b;
-  const BqLayout L = bq_layout(B, N, M);
+  const pp::PairLayout L = pp::pair_layout(B, N, M);
   const GridSet g = reinterpret_cast<const GridSet*>(ws + L.sets)[b];
   const bool usable = bq_usable(g, rpad);
   if (tile == 0 && threadIdx.x == 0)  // the scan kernel, launched next, skips the sets served here
@@ -145,7 +102,7 @@ __global__ __launch_bounds__(64) void bq_query_kernel(const float* __restrict__ 
   const unsigned* __restrict__ cell_start =
       reinterpret_cast<const unsigned*>(ws + L.cell_start) + (size_t)b * (kGridCells + 1);
   const pp::f4* __restrict__ sorted = reinterpret_cast<const pp::f4*>(ws + L.sorted) + (size_t)b * N;
-  const pp::f4* __restrict__ csorted = reinterpret_cast<const pp::f4*>(ws + L.csorted) + (size_t)b * M;
+  const pp::f4* __restrict__ csorted = reinterpret_cast<const pp::f4*>(ws + L.qsorted) + (size_t)b * M;
   const float* __restrict__ cloud = xyz + (size_t)b * N * 3;
   constexpr int G = 64 / LPC;
   const int lane = threadIdx.x;
@@ -428,7 +385,7 @@ extern "C" size_t pp_ball_query_workspace_bytes(int B, int N, int M, int nsample
   if (B <= 0 || M <= 0 || N < (g_bq_grid_mode == 2 ? 2048 : 4096) || N > kBqMaxN || nsample < 1) return 0;
   if ((long long)B * N >= (1LL << 31) || (long long)B * M >= (1LL << 31)) return 0;
   if (bq_query_lds(N, nsample, 16) > 128 * 1024) return 0;  // it has to fit (with the static LDS)
-  return bq_layout(B, N, M).total;
+  return pp::pair_layout(B, N, M).total;
 }
 
 template <typename IT, int LPC>
@@ -458,20 +415,12 @@ extern "C" int pp_ball_query_ws_f32(const float* new_xyz, const float* xyz, int*
   unsigned char* ws = (unsigned char*)workspace;
   const float radius2 = radius * radius;  // fp32, as the reference (sampling_cuda.cu:354)
   const float rpad = radius * 1.00001f + 1e-30f;
-  static pp::DeviceFlags lds_ok;
-  const size_t lds = pp::grid_build_lds_bytes(pp::kBuildSlabs) > pp::grid_build_fast_lds_bytes() ? pp::grid_build_lds_bytes(pp::kBuildSlabs)
-                                                                                                 : pp::grid_build_fast_lds_bytes();
-  static pp::DeviceFlags lds_ok_vec;
-  const bool vec = pp::clouds_vec_aligned(xyz, N, B) && pp::clouds_vec_aligned(new_xyz, M, B);
-  hipError_t e = vec ? pp::allow_big_lds(bq_build_kernel<true>, (int)lds, lds_ok_vec) : pp::allow_big_lds(bq_build_kernel<false>, (int)lds, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  (vec ? bq_build_kernel<true> : bq_build_kernel<false>)<<<dim3(8 * ((2 * B * pp::kBuildSlabs + 7) / 8)), dim3(kBuildThreads), lds, s>>>(xyz, new_xyz, ws, B, N, M);
-  PP_RETURN_IF_LAUNCH_FAILED();
+  int rc = pp::pair_build_launch(xyz, new_xyz, ws, B, N, M, s);
+  if (rc != PP_OK) return rc;
   // lanes per centre: 4 unless forced (tuning knob; at config 4, with the 14 KB footprint of round 4: 1 -> 0.122 ms,
   // 2 -> 0.115, 4 -> 0.111, 8 -> see DESIGN 5.3b)
   int lpc = g_bq_lpc ? g_bq_lpc : 4;
   while (lpc < 8 && bq_query_lds(N, nsample, 64 / lpc) > 128 * 1024) lpc *= 2;  // fewer rows per wave if the LDS is short
-  int rc;
   if (N <= 65536)
     rc = lpc == 1 ? bq_launch_query<unsigned short, 1>(xyz, idx, ws, B, N, M, radius2, rpad, nsample, s)
        : lpc == 2 ? bq_launch_query<unsigned short, 2>(xyz, idx, ws, B, N, M, radius2, rpad, nsample, s)
@@ -483,7 +432,7 @@ extern "C" int pp_ball_query_ws_f32(const float* new_xyz, const float* xyz, int*
        : lpc == 4 ? bq_launch_query<unsigned, 4>(xyz, idx, ws, B, N, M, radius2, rpad, nsample, s)
                   : bq_launch_query<unsigned, 8>(xyz, idx, ws, B, N, M, radius2, rpad, nsample, s);
   if (rc != PP_OK) return rc;
-  const BqLayout L = bq_layout(B, N, M);
+  const pp::PairLayout L = pp::pair_layout(B, N, M);
   return pp::ball_query_scan_unusable(new_xyz, xyz, idx, B, N, M, radius, nsample,
                                       reinterpret_cast<const GridSet*>(ws + L.sets), s);
 }

@@ -427,8 +427,8 @@ struct BuildPlan {
 // (NaN -> 0, +-inf -> the rim).  The Chamfer build (REFINE) keeps the old rule: there the reference's "first point
 // unconditionally" makes a non-finite point at index 0 selectable, which only the every-pair order reproduces.
 // OUT OF LINE, the points read again from memory: inlined -- the same arithmetic on the points the builds hold in
-// registers -- it cost every build 350 bytes of scratch per thread on the path that never takes it (bq_build_kernel
-// 19.8 -> 24.7 us).  Called by every thread of the workgroup; leaves in s_box: [0..2] -min, [3..5] max, [8..13] the
+// registers -- it cost every build 350 bytes of scratch per thread on the path that never takes it (ball_query's
+// build 19.8 -> 24.7 us).  Called by every thread of the workgroup; leaves in s_box: [0..2] -min, [3..5] max, [8..13] the
 // sums of x, y, z, x^2, y^2, z^2, [14] the number of finite points (the same values in every workgroup of the set: the
 // slabs' plans must agree, and they do -- same data, same order).  The caller reads them and meets a barrier.
 __device__ __attribute__((noinline)) void plain_finite_plan(const float* __restrict__ ref, int nr, float* s_box) {

@@ -8,17 +8,16 @@
 // (0, 0), as do the rows of queries beyond lengths1 (pytorch3d pads with zeros).
 //   * knn_scan_kernel<KT>: one lane per query, reference point wave-uniform, sorted K-list in registers.
 //   * knn_grid_kernel<KT>: the exact grid search of three_nn_grid.hip with a K-list: reference points
-//     counting-sorted into the grid, queries Morton-sorted, a lane scans the cell box
+//     counting-sorted into the grid, queries Morton-sorted (grid_pairs.hip), a lane scans the cell box
 //     [cell(q - R), cell(q + R)] and stops when its K-th best is below 0.9999 reach^2 (reach = what the
-//     rounded box bounds guarantee on every axis); otherwise R doubles.  Same bits as the scan.
-#include "grid_common.h"
+//     rounded box bounds guarantee on every axis); otherwise R grows.  Same bits as the scan.
+#include "grid_pairs.h"
 
 namespace {
 
 using pp::GridSet;
 using pp::cell_coord;
 using pp::kGridCells;
-using pp::kBuildThreads;
 
 // ascending K-list in registers; (d, k) enters if it is lexicographically smaller than an entry
 template <int KT>
@@ -236,46 +235,6 @@ __global__ __launch_bounds__(256) void knn_nd_kernel(const float* __restrict__ p
   knn_store<KT>(L, od, oi, K, m2);
 }
 
-struct KnLayout {
-  size_t sets, cell_start, sorted, qsorted, total;
-};
-__host__ __device__ inline KnLayout kn_layout(int B, int N, int M) {
-  KnLayout L;
-  L.sets = 0;  // [2B]: sets of the reference clouds, then the (unused) sets of the query sort
-  L.cell_start = ((size_t)64 * 2 * B + 255) / 256 * 256;
-  L.sorted = L.cell_start + ((size_t)4 * (kGridCells + 1) * B + 255) / 256 * 256;
-  L.qsorted = L.sorted + ((size_t)16 * B * M + 255) / 256 * 256;
-  L.total = L.qsorted + (size_t)16 * B * N;
-  return L;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kBuildThreads) void kn_build_kernel(const float* __restrict__ p2,
-                                                                 const float* __restrict__ p1,
-                                                                 unsigned char* __restrict__ ws, int B, int N,
-                                                                 int M) {
-  extern __shared__ __attribute__((aligned(16))) unsigned s_cnt[];
-  const KnLayout L = kn_layout(B, N, M);
-  // both sets of a batch element are built on the XCD that will search it (the query kernel's batch ->
-  // XCD mapping): virtual order (batch, cloud | queries, slab)
-  const int V = pp::xcd_virtual_block(blockIdx.x, (2 * B * pp::kBuildSlabs + 7) / 8);
-  if (V >= 2 * B * pp::kBuildSlabs) return;
-  const int slab = V % pp::kBuildSlabs;
-  const int set = ((V / pp::kBuildSlabs) & 1) * B + V / (2 * pp::kBuildSlabs);
-  GridSet* gs = reinterpret_cast<GridSet*>(ws + L.sets) + set;
-  if (set >= B) {
-    const int b = set - B;
-    pp::grid_build_set<true, VEC>(p1 + (size_t)b * N * 3, N, gs, nullptr,
-                             reinterpret_cast<pp::f4*>(ws + L.qsorted) + (size_t)b * N, nullptr, s_cnt, nullptr,
-                             nullptr, slab, pp::kBuildSlabs);
-    return;
-  }
-  const int b = set;
-  pp::grid_build_set_plain<VEC>(p2 + (size_t)b * M * 3, M, gs,
-                                reinterpret_cast<unsigned*>(ws + L.cell_start) + (size_t)b * (kGridCells + 1),
-                                reinterpret_cast<pp::f4*>(ws + L.sorted) + (size_t)b * M, s_cnt, slab, pp::kBuildSlabs);
-}
-
 template <int KT>
 __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                        float* __restrict__ dist, int* __restrict__ idx,
@@ -285,7 +244,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
   if (vb >= B * tiles_per_b) return;
   const int b = vb / tiles_per_b;
   const int tile = vb - b * tiles_per_b;
-  const KnLayout L = kn_layout(B, N, M);
+  const pp::PairLayout L = pp::pair_layout(B, M, N);
   const GridSet g = reinterpret_cast<const GridSet*>(ws + L.sets)[b];
   const bool usable = !pp::grid_useless(g);
   const int n = tile * 256 + threadIdx.x;
@@ -315,20 +274,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
   const bool finite_q = __builtin_isfinite(q.x) && __builtin_isfinite(q.y) && __builtin_isfinite(q.z);
   // first box: about 2K points expected if the cloud filled its cells evenly (2 per cell), at least one cell
   float R = finite_q ? g.h * fmaxf(1.0f, 0.5f * cbrtf((float)K)) : 2.0e38f;
-#ifndef PP_KNN_KEY64
-#define PP_KNN_KEY64 1
-#endif
-#ifndef PP_KNN_BALL
-#define PP_KNN_BALL 1  // rounds after the first walk the ball of the K-th best found, not its box (0: the box)
-#endif
-#ifndef PP_KNN_FLY
-#define PP_KNN_FLY 2
-#endif
-#if PP_KNN_KEY64
   KList64<KT> Lk;
-#else
-  KList<KT> Lk;
-#endif
   const int kth = min(K, M) - 1;  // the entry that decides when to stop
   // (round 5) from the second round on only the BALL of the K-th best of the round before can matter, not its box: rows
   // beyond it are passed over, the others cut along x (three_nn_grid.hip / chamfer_grid.hip's ball stages: same rule)
@@ -351,20 +297,16 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
       for (int y = y0; y <= y1; ++y) {
         const int c = (z * g.gy + y) * g.gx;
         int xa = x0, xb = x1;
-#if PP_KNN_BALL
-        {
-          if (bk2 < 3.0e38f && !everything) {  // (a lane in its first round has no bound yet: nothing of this for it)
-            const float dy = y < cy ? py - (float)(y + 1) : (y > cy ? (float)y - py : 0.0f);
-            const float dz = z < cz ? pz - (float)(z + 1) : (z > cz ? (float)z - pz : 0.0f);
-            const float w2 = bk2 - (dy * dy + dz * dz);
-            if (w2 < 0.0f) continue;  // the row lies beyond the ball
-            const float w = __builtin_amdgcn_sqrtf(w2) * 1.00001f;
-            xa = max(xa, max(min((int)(px - w), g.gx - 1), 0));
-            xb = min(xb, max(min((int)(px + w), g.gx - 1), 0));
-            if (xa > xb) continue;
-          }
+        if (bk2 < 3.0e38f && !everything) {  // (a lane in its first round has no bound yet: nothing of this for it)
+          const float dy = y < cy ? py - (float)(y + 1) : (y > cy ? (float)y - py : 0.0f);
+          const float dz = z < cz ? pz - (float)(z + 1) : (z > cz ? (float)z - pz : 0.0f);
+          const float w2 = bk2 - (dy * dy + dz * dz);
+          if (w2 < 0.0f) continue;  // the row lies beyond the ball
+          const float w = __builtin_amdgcn_sqrtf(w2) * 1.00001f;
+          xa = max(xa, max(min((int)(px - w), g.gx - 1), 0));
+          xb = min(xb, max(min((int)(px + w), g.gx - 1), 0));
+          if (xa > xb) continue;
         }
-#endif
         // (one 16-byte load for both bounds of a row up to three cells wide: see three_nn_grid.hip)
         typedef unsigned u4 __attribute__((ext_vector_type(4)));
         u4 v;
@@ -372,7 +314,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
         const int wd = xb + 1 - xa;
         unsigned e = wd == 1 ? v.y : (wd == 2 ? v.z : v.w);
         if (wd > 3) e = cell_start[c + xb + 1];
-        constexpr int kFly = PP_KNN_FLY;  // loads in flight per lane (the tail of a row repeats its last point)
+        constexpr int kFly = 2;  // loads in flight per lane (the tail of a row repeats its last point)
         for (unsigned i = v.x; i < e; i += kFly) {
           pp::f4 pf[kFly];
 #pragma unroll
@@ -382,26 +324,15 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
             const pp::f4 p = pf[u];
             const float d = pp::chamfer_d3(p.x, p.y, p.z, q.x, q.y, q.z);
             const int id = __float_as_int(p.w);
-#if PP_KNN_KEY64
             const unsigned long long nk = (u == 0 || i + u < e) ? KList64<KT>::key(d, id) : ~0ull;  // (~0: never enters)
             if (Lk.beats_last(nk)) Lk.insert(nk);
-#else
-            if (u == 0 || i + u < e)
-              if (Lk.beats_last(d, id)) Lk.insert(d, id);
-#endif
           }
         }
       }
     const bool whole = x0 == 0 && y0 == 0 && z0 == 0 && x1 == g.gx - 1 && y1 == g.gy - 1 && z1 == g.gz - 1;
-#if PP_KNN_KEY64
     float dk = Lk.dist(0);
 #pragma unroll
     for (int j = 1; j < KT; ++j) dk = j <= kth ? Lk.dist(j) : dk;
-#else
-    float dk = Lk.d[0];
-#pragma unroll
-    for (int j = 1; j < KT; ++j) dk = j <= kth ? Lk.d[j] : dk;
-#endif
     if (whole || dk < 0.9999f * (reach * reach)) break;
     // the next box: the K-th best found so far bounds the answer, so a box of half-width sqrt(dk) (+ 0.05 %) ends the
     // search -- doubling blindly walked 125 cells where a few dozen do (three_nn_grid.hip: the same); at least 25 %
@@ -409,7 +340,6 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
     R = dk < 3.0e38f ? fmaxf(sqrtf(dk) * 1.0005f, 1.25f * R) : 2.0f * R;
     bk2 = dk < 3.0e38f ? dk * (g.invh * g.invh) * (1.0f / 0.999f) : __builtin_inff();
   }
-#if PP_KNN_KEY64
   KList<KT> out;
 #pragma unroll
   for (int j = 0; j < KT; ++j) {
@@ -417,9 +347,16 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
     out.i[j] = Lk.index(j);
   }
   knn_store<KT>(out, dist + ((size_t)b * N + qorig) * K, idx + ((size_t)b * N + qorig) * K, K, M);
-#else
-  knn_store<KT>(Lk, dist + ((size_t)b * N + qorig) * K, idx + ((size_t)b * N + qorig) * K, K, M);
-#endif
+}
+
+// the K-list sizes that are compiled: f(the smallest one that holds K), as a compile-time constant
+template <typename F>
+int knn_with_list_size(int K, F f) {
+  if (K <= 1) return f(std::integral_constant<int, 1>{});
+  if (K <= 4) return f(std::integral_constant<int, 4>{});
+  if (K <= 8) return f(std::integral_constant<int, 8>{});
+  if (K <= 16) return f(std::integral_constant<int, 16>{});
+  return f(std::integral_constant<int, 32>{});
 }
 
 template <int KT>
@@ -436,11 +373,9 @@ int knn_scan_launch(const float* p1, const float* p2, const int* len1, const int
 
 int knn_scan_dispatch(const float* p1, const float* p2, const int* len1, const int* len2, float* dist, int* idx,
                       int B, int N, int M, int K, const GridSet* skip, hipStream_t s) {
-  if (K <= 1) return knn_scan_launch<1>(p1, p2, len1, len2, dist, idx, B, N, M, K, skip, s);
-  if (K <= 4) return knn_scan_launch<4>(p1, p2, len1, len2, dist, idx, B, N, M, K, skip, s);
-  if (K <= 8) return knn_scan_launch<8>(p1, p2, len1, len2, dist, idx, B, N, M, K, skip, s);
-  if (K <= 16) return knn_scan_launch<16>(p1, p2, len1, len2, dist, idx, B, N, M, K, skip, s);
-  return knn_scan_launch<32>(p1, p2, len1, len2, dist, idx, B, N, M, K, skip, s);
+  return knn_with_list_size(K, [&](auto kt) {
+    return knn_scan_launch<decltype(kt)::value>(p1, p2, len1, len2, dist, idx, B, N, M, K, skip, s);
+  });
 }
 
 template <int KT>
@@ -476,7 +411,7 @@ extern "C" int pp_knn_f32(const float* p1, const float* p2, const int* lengths1,
 extern "C" size_t pp_knn_workspace_bytes(int B, int N, int M, int K) {
   if (B <= 0 || N < 1024 || M < 1024 || K < 1 || K > 32 || M < 4 * K) return 0;
   if ((long long)B * N >= (1LL << 31) || (long long)B * M >= (1LL << 31)) return 0;
-  return kn_layout(B, N, M).total;
+  return pp::pair_layout(B, M, N).total;
 }
 
 extern "C" int pp_knn_ws_f32(const float* p1, const float* p2, const int* lengths1, const int* lengths2,
@@ -489,21 +424,12 @@ extern "C" int pp_knn_ws_f32(const float* p1, const float* p2, const int* length
   if (!knn_args_ok(p1, p2, dist2, idx, B, N, M, K)) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
-  static pp::DeviceFlags lds_ok;
-  const size_t lds = pp::grid_build_lds_bytes(pp::kBuildSlabs) > pp::grid_build_fast_lds_bytes() ? pp::grid_build_lds_bytes(pp::kBuildSlabs)
-                                                                                                 : pp::grid_build_fast_lds_bytes();
-  static pp::DeviceFlags lds_ok_vec;
-  const bool vec = pp::clouds_vec_aligned(p1, N, B) && pp::clouds_vec_aligned(p2, M, B);
-  hipError_t e = vec ? pp::allow_big_lds(kn_build_kernel<true>, (int)lds, lds_ok_vec) : pp::allow_big_lds(kn_build_kernel<false>, (int)lds, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  (vec ? kn_build_kernel<true> : kn_build_kernel<false>)<<<dim3(8 * ((2 * B * pp::kBuildSlabs + 7) / 8)), dim3(kBuildThreads), lds, s>>>(p2, p1, ws, B, N, M);
-  PP_RETURN_IF_LAUNCH_FAILED();
+  const int rc = pp::pair_build_launch(p2, p1, ws, B, M, N, s);
+  if (rc != PP_OK) return rc;
   // (batch elements whose grid is of no use are served by the same kernel, every pair: no second launch)
-  if (K <= 1) return knn_grid_launch<1>(p1, p2, dist2, idx, ws, B, N, M, K, s);
-  if (K <= 4) return knn_grid_launch<4>(p1, p2, dist2, idx, ws, B, N, M, K, s);
-  if (K <= 8) return knn_grid_launch<8>(p1, p2, dist2, idx, ws, B, N, M, K, s);
-  if (K <= 16) return knn_grid_launch<16>(p1, p2, dist2, idx, ws, B, N, M, K, s);
-  return knn_grid_launch<32>(p1, p2, dist2, idx, ws, B, N, M, K, s);
+  return knn_with_list_size(K, [&](auto kt) {
+    return knn_grid_launch<decltype(kt)::value>(p1, p2, dist2, idx, ws, B, N, M, K, s);
+  });
 }
 
 // pytorch3d.ops.knn_points for any point dimension D (1 <= D <= 512) and 1 <= K <= 128: brute force with the

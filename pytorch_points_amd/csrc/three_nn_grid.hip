@@ -5,70 +5,24 @@
 // three smallest pairs (dist3, index) in lexicographic order.
 //
 // The known points of a batch element are counting-sorted into the grid (cell side h); the unknown
-// points are sorted along a Morton curve so that the lanes of a wave walk neighbouring cells.  A
+// points are sorted along a Morton curve so that the lanes of a wave walk neighbouring cells
+// (both by grid_pairs.hip).  A
 // lane searches the cell box [cell(q - R), cell(q + R)], R = h first, keeping the three smallest
 // (dist3, index) pairs of the box (same arithmetic as the scan: pp::dist3).  A known point outside
 // that box lies beyond one of the (rounded) bounds q -+ R along some axis (the cell coordinate is
 // monotone in the coordinate), so it differs from q by more than reach = min over the axes of
 // fl(q + R) - q and q - fl(q - R), and its fp32 dist3 is >= reach^2 (1 - 1e-6): once the third
 // best is < 0.9999 reach^2 no outside point can enter the result or tie with it, and the lane is
-// done.  (reach, not R: coordinates may be large against the cell size.)  Otherwise R doubles
+// done.  (reach, not R: coordinates may be large against the cell size.)  Otherwise R grows
 // and the lane searches again; a box that covers the whole grid ends the search unconditionally
 // (that is the scan).  Batch elements whose grid is useless go to the scan kernel.
-#include "grid_common.h"
-
-#ifndef PP_TN_BALL
-#define PP_TN_BALL 1  // rounds after the first walk the ball of the third best found, not its box (0: the box)
-#endif
+#include "grid_pairs.h"
 
 namespace {
 
 using pp::GridSet;
 using pp::cell_coord;
 using pp::kGridCells;
-using pp::kBuildThreads;
-
-struct TnLayout {
-  size_t sets, cell_start, sorted, qsorted, total;
-};
-__host__ __device__ inline TnLayout tn_layout(int B, int N, int M) {
-  TnLayout L;
-  L.sets = 0;  // [2B]: sets of the known clouds, then the (unused) sets of the query sort
-  L.cell_start = ((size_t)64 * 2 * B + 255) / 256 * 256;
-  L.sorted = L.cell_start + ((size_t)4 * (kGridCells + 1) * B + 255) / 256 * 256;
-  L.qsorted = L.sorted + ((size_t)16 * B * M + 255) / 256 * 256;
-  L.total = L.qsorted + (size_t)16 * B * N;
-  return L;
-}
-
-// workgroups [0, S*B): slab s of the known points of batch element b into their grid; [S*B, 2*S*B):
-// slab s of the unknown points of batch element b into Morton order (S = kBuildSlabs)
-template <bool VEC>
-__global__ __launch_bounds__(kBuildThreads) void tn_build_kernel(const float* __restrict__ known,
-                                                                 const float* __restrict__ unknown,
-                                                                 unsigned char* __restrict__ ws, int B, int N,
-                                                                 int M) {
-  extern __shared__ __attribute__((aligned(16))) unsigned s_cnt[];
-  const TnLayout L = tn_layout(B, N, M);
-  // both sets of a batch element are built on the XCD that will search it (the query kernel's batch ->
-  // XCD mapping): virtual order (batch, cloud | queries, slab)
-  const int V = pp::xcd_virtual_block(blockIdx.x, (2 * B * pp::kBuildSlabs + 7) / 8);
-  if (V >= 2 * B * pp::kBuildSlabs) return;
-  const int slab = V % pp::kBuildSlabs;
-  const int set = ((V / pp::kBuildSlabs) & 1) * B + V / (2 * pp::kBuildSlabs);
-  GridSet* gs = reinterpret_cast<GridSet*>(ws + L.sets) + set;
-  if (set >= B) {
-    const int b = set - B;
-    pp::grid_build_set<true, VEC>(unknown + (size_t)b * N * 3, N, gs, nullptr,
-                             reinterpret_cast<pp::f4*>(ws + L.qsorted) + (size_t)b * N, nullptr, s_cnt, nullptr,
-                             nullptr, slab, pp::kBuildSlabs);
-    return;
-  }
-  const int b = set;
-  pp::grid_build_set_plain<VEC>(known + (size_t)b * M * 3, M, gs,
-                                reinterpret_cast<unsigned*>(ws + L.cell_start) + (size_t)b * (kGridCells + 1),
-                                reinterpret_cast<pp::f4*>(ws + L.sorted) + (size_t)b * M, s_cnt, slab, pp::kBuildSlabs);
-}
 
 // (d, k) enters the ascending triple if it is lexicographically smaller than an entry -- the reference's strict `<` in
 // index order.  With (distance bits << 32 | index) keys: for distances >= +0 that are not NaN the unsigned order of the
@@ -91,7 +45,7 @@ __global__ __launch_bounds__(256) void tn_query_kernel(const float* __restrict__
   if (vb >= B * tiles_per_b) return;
   const int b = vb / tiles_per_b;
   const int tile = vb - b * tiles_per_b;
-  const TnLayout L = tn_layout(B, N, M);
+  const pp::PairLayout L = pp::pair_layout(B, M, N);
   const GridSet g = reinterpret_cast<const GridSet*>(ws + L.sets)[b];
   const bool usable = !pp::grid_useless(g);
   const int n = tile * 256 + threadIdx.x;
@@ -159,20 +113,16 @@ __global__ __launch_bounds__(256) void tn_query_kernel(const float* __restrict__
       for (int y = y0; y <= y1; ++y) {
         const int c = (z * g.gy + y) * g.gx;
         int xa = x0, xb = x1;
-#if PP_TN_BALL
-        {
-          if (bk2 < 3.0e38f && !everything) {  // (a lane in its first round has no bound yet: nothing of this for it)
-            const float dy = y < cy ? py - (float)(y + 1) : (y > cy ? (float)y - py : 0.0f);
-            const float dz = z < cz ? pz - (float)(z + 1) : (z > cz ? (float)z - pz : 0.0f);
-            const float w2 = bk2 - (dy * dy + dz * dz);
-            if (w2 < 0.0f) continue;  // the row lies beyond the ball
-            const float w = __builtin_amdgcn_sqrtf(w2) * 1.00001f;
-            xa = max(xa, max(min((int)(px - w), g.gx - 1), 0));
-            xb = min(xb, max(min((int)(px + w), g.gx - 1), 0));
-            if (xa > xb) continue;
-          }
+        if (bk2 < 3.0e38f && !everything) {  // (a lane in its first round has no bound yet: nothing of this for it)
+          const float dy = y < cy ? py - (float)(y + 1) : (y > cy ? (float)y - py : 0.0f);
+          const float dz = z < cz ? pz - (float)(z + 1) : (z > cz ? (float)z - pz : 0.0f);
+          const float w2 = bk2 - (dy * dy + dz * dz);
+          if (w2 < 0.0f) continue;  // the row lies beyond the ball
+          const float w = __builtin_amdgcn_sqrtf(w2) * 1.00001f;
+          xa = max(xa, max(min((int)(px - w), g.gx - 1), 0));
+          xb = min(xb, max(min((int)(px + w), g.gx - 1), 0));
+          if (xa > xb) continue;
         }
-#endif
         // a row's two bounds are a few table entries apart: up to three cells wide (the usual first round)
         // ONE 16-byte load fetches both (the entries after a set's table are the next set's or the sorted
         // cloud: valid memory); this kernel is bound by the L1's handling of scattered loads
@@ -216,7 +166,7 @@ extern "C" void pp_debug_set_three_nn_search(int v) { g_tn_grid_mode.set(v); }
 extern "C" size_t pp_three_nn_workspace_bytes(int B, int N, int M) {
   if (B <= 0 || N < 1024 || M < 1024) return 0;
   if ((long long)B * N >= (1LL << 31) || (long long)B * M >= (1LL << 31)) return 0;
-  return tn_layout(B, N, M).total;
+  return pp::pair_layout(B, M, N).total;
 }
 
 extern "C" int pp_three_nn_ws_f32(const float* unknown, const float* known, float* dist2, int* idx, int B, int N,
@@ -227,15 +177,8 @@ extern "C" int pp_three_nn_ws_f32(const float* unknown, const float* known, floa
   if (!unknown || !known || !dist2 || !idx) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
-  static pp::DeviceFlags lds_ok;
-  const size_t lds = pp::grid_build_lds_bytes(pp::kBuildSlabs) > pp::grid_build_fast_lds_bytes() ? pp::grid_build_lds_bytes(pp::kBuildSlabs)
-                                                                                                 : pp::grid_build_fast_lds_bytes();
-  static pp::DeviceFlags lds_ok_vec;
-  const bool vec = pp::clouds_vec_aligned(unknown, N, B) && pp::clouds_vec_aligned(known, M, B);
-  hipError_t e = vec ? pp::allow_big_lds(tn_build_kernel<true>, (int)lds, lds_ok_vec) : pp::allow_big_lds(tn_build_kernel<false>, (int)lds, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  (vec ? tn_build_kernel<true> : tn_build_kernel<false>)<<<dim3(8 * ((2 * B * pp::kBuildSlabs + 7) / 8)), dim3(kBuildThreads), lds, s>>>(known, unknown, ws, B, N, M);
-  PP_RETURN_IF_LAUNCH_FAILED();
+  const int rc = pp::pair_build_launch(known, unknown, ws, B, M, N, s);
+  if (rc != PP_OK) return rc;
   const int tiles = (N + 255) / 256;
   const long long per_xcd = ((long long)B * tiles + 7) / 8;
   if (per_xcd * 8 > 0x7fffffffLL) return PP_EINVAL;

@@ -29,7 +29,8 @@ def _t(a, cuda):
 
 
 @pytest.mark.parametrize("K", [1, 3, 4, 8, 9, 16, 17, 32])
-@pytest.mark.parametrize("b,n,m", [(2, 2048, 2048), (1, 5000, 3001), (3, 1024, 4096)])
+@pytest.mark.parametrize("b,n,m", [(2, 2048, 2048), (1, 5000, 3001), (3, 1024, 4096),
+                                   (2, 1030, 1025)])  # (the last: clouds that are not 16-byte aligned, the other build)
 def test_knn_matches_oracle(cuda, knn_path, b, n, m, K):
     from pytorch_points_amd.ops import knn_points
     p1 = S.unit_sphere(90, b, n)
