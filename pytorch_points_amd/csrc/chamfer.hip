@@ -977,7 +977,10 @@ int zero_outputs(float* dist1, int* idx1, float* dist2, int* idx2, int B, int N,
 
 }  // namespace
 
-// Tuning override for benchmarking variants in one process (bench.py --variant); 0 = automatic.
+// Tuning override for benchmarking the forms in one process (bench.py --variant).  C == 3: 0 = automatic, which takes
+// 1 = <Q 1, G 8>, 1002 = <2, 8, packed> or 1416 = <4, 16, packed>; 416 = <4, 16>, 1008 = <8, 8, packed>, 2004 =
+// <4, 8, packed, prefetch>, 3004 = <4, 8, prefetch> are kept for tests/test_gpu_range.py, which forces them over the
+// fp32 range; any other value is PP_EINVAL.  C != 3: 9 = the one-lane-per-query kernels, every other value automatic.
 static pp::Knob g_fwd_variant;
 extern "C" void pp_debug_set_nmdistance_variant(int v) { g_fwd_variant.set(v); }
 
@@ -1013,22 +1016,12 @@ extern "C" int pp_nmdistance_forward_f32(const float* xyz1, const float* xyz2, f
     int variant = g_fwd_variant;
     if (variant == 0) variant = q >= 4LL * 256 * 1024 ? 1416 : (q >= 2LL * 256 * 512 ? 1002 : 1);
     switch (variant) {
-      case 4: return launch_fwd_c3<4, 8>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 2: return launch_fwd_c3<2, 8>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 1: return launch_fwd_c3<1, 8>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 8: return launch_fwd_c3<8, 8>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 416: return launch_fwd_c3<4, 16>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 216: return launch_fwd_c3<2, 16>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 44: return launch_fwd_c3<4, 4>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 1002: return launch_fwd_c3<2, 8, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 1004: return launch_fwd_c3<4, 8, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 1008: return launch_fwd_c3<8, 8, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 1416: return launch_fwd_c3<4, 16, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 1816: return launch_fwd_c3<8, 16, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 2004: return launch_fwd_c3<4, 8, true, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 2008: return launch_fwd_c3<8, 8, true, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 2002: return launch_fwd_c3<2, 8, true, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 2416: return launch_fwd_c3<4, 16, true, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 3004: return launch_fwd_c3<4, 8, false, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       default: return PP_EINVAL;
     }
@@ -1103,8 +1096,9 @@ extern "C" int pp_labeled_nmdistance_forward_f32(const float* xyz1, const float*
   return PP_OK;
 }
 
-// 0 = automatic (double LDS accumulators for C == 3); 1 = force the global-atomic form; 2 = force
-// the fp32 LDS-column form; 3 = the CSR form; 4 = same as 0   (tests and tuning)
+// 0 = automatic (double LDS accumulators for C == 3, N + M >= 4096); 1 = force the global-atomic form; 2 = force
+// the fp32 LDS-column form; 4 = same as 0; 3 and every other value = skip the double accumulators, i.e. the CSR
+// form where it applies   (tests and tuning)
 static pp::Knob g_bwd_variant;
 extern "C" void pp_debug_set_nmdistance_backward_variant(int v) { g_bwd_variant.set(v); }
 

@@ -18,8 +18,8 @@
 //   * clouds that are not evenly sampled surfaces (everything below stays inside the two launches):
 //       - a cell holding more than kCrowd points (clusters, several scales) carries a grid of its own
 //         (grid_common.h: SubGrid); queries whose block touches one search it through that grid;
-//       - a wave in which many queries are open after the 2x2x2 block (thin regions) runs the cubes of radius
-//         1 and 2 a lane per query, otherwise the whole wave serves them one by one;
+//       - the queries open after the 2x2x2 block (thin regions) go through the balls around their candidates and the
+//         cubes of radius 1 and 2, the rows of both pooled over the wave (wave_pooled_ball_search);
 //       - a query that cannot stop at rho = 2 (far from the reference cloud: clusters at different places,
 //         disjoint clouds, the tail of a Gaussian) joins a group of such queries of its wave that lie close
 //         together; the wave stages the cell rows the group can need -- bounded by the best candidate its
@@ -481,7 +481,6 @@ typedef float __attribute__((address_space(3))) * lds_f_wptr;
 
 // helpers of the search kernels' in-kernel fallbacks (no brute-force list, no third launch)
 constexpr int kStageLayers = 8;
-constexpr int kLaneCubeMaxGroups = 48;  // groups of four points a lane walks per four rows of a cube before it gives up
 constexpr int kSubMaxRho = 2;  // widest cube of sub-cells a lane examines inside a crowded cell
 constexpr int kGroupBatch = 256;  // candidates per LDS batch of wave_group_search (<= the smallest per-wave slice)
 // a blind seed's group: the open queries within this fraction of its candidate's distance (round 3: 1/4 made groups as
@@ -491,16 +490,14 @@ constexpr float kBlindGroup = 0.35f;  // (round 6, with the nearest-first parts 
 // The constants of the stages behind stage A, as round 5's A/B runs settled them (each was a -D switch of a variant
 // library then: profiles/r5/near_field_stages_ab.txt; frozen in round 6).  The forms they chose between and that lost --
 // a lane per query instead of the pooled ball / cube, no ball after the cubes, a lane per query for labeled searches --
-// are gone from the dispatch; lane_ball_search remains for the wave slices below 384 points.
+// are gone.
 constexpr int kMemberCutMin = 2;    // (round 5: 2, was 8 -- disjoint clouds 0.225 -> 0.203 ms) candidates per member the pieces' cuts must leave in a block of rows for the member-by-member cut
 constexpr float kBallRmax = 2.5f;   // cells: the farthest candidate whose ball is walked (a box of at most 6 x 6 rows)
 constexpr int kPoolCubeMin = 1;
 constexpr int kPoolMin = 1;         // ... pooled over the wave (unlabeled searches)
-constexpr int kBallMin = 6;         // lanes with a candidate from which the ball around it is walked a lane per query
 constexpr int kSerialFar = 8;
 constexpr int kSerialMax = 24;      // open lanes of a wave from which the whole-wave cubes are skipped for the group search
 constexpr int kOpenJoin = 16;       // open lanes of a wave from which its pending lanes go to the group search with them
-constexpr int kLaneStageMin = 6;    // open lanes of a wave from which the cubes are searched a lane per query
 
 // distance (in cells) from a query at position f inside cell c to the nearer face of its 2-cell block along one
 // axis that has grid beyond it (s = -1: the block is cells c-1, c; +1: c, c+1; beyond the grid there is nothing)
@@ -660,7 +657,7 @@ __device__ __forceinline__ float sub_cell_search(const pp::SubGrid sg, const uns
 struct Found {
   float best;
   int bidx;
-  float aux;  // lane_cube_search: 1 settled, 0 not, 2 gave up; refined_block_search: the threshold it reached
+  float aux;  // wave_pooled_ball_search: 1 settled, 0 not, 2 gave up; refined_block_search: the threshold it reached
 };
 // The whole-wave cubes for the queries whose scans are long (rows through crowded cells), one after the other, with
 // the pipelined scan.  Out of line; never called for evenly sampled surfaces.  (The grid's descriptor by POINTER:
@@ -1386,189 +1383,16 @@ __device__ __attribute__((noinline)) Found wave_group_search(const GridSet g, co
   return o;
 }
 
-// A cube of Chebyshev radius rho around the query's cell, a LANE per query (waves in which many lanes are open
-// after stage A: the thin parts of a cloud, the sparse scale of a two-scale cloud): the cube's (2 rho + 1)^2 rows
-// four at a time, each four as one sequence of groups like stage A, candidates from global memory in the exact
-// (distance, index) order.  Returns whether the cube settles the lane's query; (best, bidx) carry on.
-struct RowSpan {
-  unsigned s, e;
-};
-__device__ __forceinline__ RowSpan cube_row(int r, int nrows, int side, int rho, int cy, int cz, int x0, int x1,
-                                            bool active, const GridSet& g, const unsigned* __restrict__ cell_start) {
-  const int z = cz - rho + r / side, y = cy - rho + r % side;
-  const bool ok = active && r < nrows && z >= 0 && z < g.gz && y >= 0 && y < g.gy;
-  const int c = pp::cell_linear(0, min(max(y, 0), g.gy - 1), min(max(z, 0), g.gz - 1), g.gx, g.gy);
-  RowSpan o;
-  o.s = ok ? cell_start[c + x0] : 0u;
-  o.e = ok ? cell_start[c + x1 + 1] : 0u;
-  return o;
-}
-
-template <bool LAB, int W>
-__device__ __attribute__((noinline)) Found lane_cube_search(const GridSet g, const unsigned* __restrict__ cell_start,
-                                                            const pp::f4* __restrict__ sorted,
-                                                            const float* __restrict__ slab, float qx, float qy, float qz,
-                                                            float ql, int rho, bool active, float best_in, int bidx_in) {
-  const int cx = cell_coord(qx, g.minx, g.invh, g.gx);
-  const int cy = cell_coord(qy, g.miny, g.invh, g.gy);
-  const int cz = cell_coord(qz, g.minz, g.invh, g.gz);
-  const float fx = (qx - g.minx) * g.invh - (float)cx, fy = (qy - g.miny) * g.invh - (float)cy,
-              fz = (qz - g.minz) * g.invh - (float)cz;
-  const int x0 = max(cx - rho, 0), x1 = min(cx + rho, g.gx - 1);
-  const int side = 2 * rho + 1, nrows = side * side;
-  float best = best_in;
-  int bidx = bidx_in;
-  bool gave_up = false;
-  for (int r0 = 0; r0 < nrows; r0 += 4) {  // wave-uniform
-    const RowSpan a0 = cube_row(r0, nrows, side, rho, cy, cz, x0, x1, active, g, cell_start);
-    const RowSpan a1 = cube_row(r0 + 1, nrows, side, rho, cy, cz, x0, x1, active, g, cell_start);
-    const RowSpan a2 = cube_row(r0 + 2, nrows, side, rho, cy, cz, x0, x1, active, g, cell_start);
-    const RowSpan a3 = cube_row(r0 + 3, nrows, side, rho, cy, cz, x0, x1, active, g, cell_start);
-    unsigned t0 = (a0.e - a0.s + 3) >> 2, t1 = (a1.e - a1.s + 3) >> 2, t2 = (a2.e - a2.s + 3) >> 2,
-             t3 = (a3.e - a3.s + 3) >> 2;
-    // a lane whose rows run through a crowded cell would keep the whole wave waiting on its loads, one lane's
-    // worth at a time: it gives up and is served by the whole wave afterwards
-    if (t0 + t1 + t2 + t3 > (unsigned)kLaneCubeMaxGroups) {
-      gave_up = true;
-      t0 = t1 = t2 = t3 = 0u;
-    }
-    const unsigned T1 = t0, T2 = T1 + t1, T3 = T2 + t2, T4 = T3 + t3;
-    const unsigned adj0 = a0.s, adj1 = a1.s - 4 * T1, adj2 = a2.s - 4 * T2, adj3 = a3.s - 4 * T3;
-    const unsigned last0 = a0.e - 1, last1 = a1.e - 1, last2 = a2.e - 1, last3 = a3.e - 1;
-    pp::f4 pa[4], pb[4];
-    float la[4] = {0.0f, 0.0f, 0.0f, 0.0f}, lb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    stage_a_fetch<LAB>(0, T1, T2, T3, T4, adj0, adj1, adj2, adj3, last0, last1, last2, last3, sorted, slab, pa, la);
-    for (unsigned k = 0; __any(k < T4); k += 2) {
-      stage_a_fetch<LAB>(k + 1, T1, T2, T3, T4, adj0, adj1, adj2, adj3, last0, last1, last2, last3, sorted, slab, pb, lb);
-      if (k < T4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) take_candidate<LAB>(pa[u], la[u], qx, qy, qz, ql, best, bidx);
-      }
-      stage_a_fetch<LAB>(k + 2, T1, T2, T3, T4, adj0, adj1, adj2, adj3, last0, last1, last2, last3, sorted, slab, pa, la);
-      if (k + 1 < T4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) take_candidate<LAB>(pb[u], lb[u], qx, qy, qz, ql, best, bidx);
-      }
-    }
-  }
-  auto axis = [&](float f, int c, int gdim) {
-    const float lo = c - rho >= 1 ? (float)rho + f : __builtin_inff();
-    const float hi = c + rho <= gdim - 2 ? (float)(rho + 1) - f : __builtin_inff();
-    return fminf(lo, hi);
-  };
-  const float reach = g.h * fminf(axis(fx, cx, g.gx), fminf(axis(fy, cy, g.gy), axis(fz, cz, g.gz)));
-  const bool all = cz - rho <= 0 && cz + rho >= g.gz - 1 && cy - rho <= 0 && cy + rho >= g.gy - 1 && cx - rho <= 0 &&
-                   cx + rho >= g.gx - 1;
-  const bool settled = all ? (LAB || bidx != 0x7fffffff) : (best < reach * reach * kBoundSlack);
-  Found o;
-  o.best = active ? best : best_in;
-  o.bidx = active ? bidx : bidx_in;
-  if (LAB && active && settled && !gave_up && bidx == 0x7fffffff) {  // whole grid examined, nobody carries this label
-    o.best = 0.0f;                                         // (ref nmdistance_cuda.cu:110-113)
-    o.bidx = -1;
-  }
-  o.aux = gave_up ? 2.0f : ((settled && active) ? 1.0f : 0.0f);  // (candidates seen before giving up stay valid)
-  return o;
-}
-
 // Round 5 -- the BALL around a query that already holds a candidate (its block was not empty, only too small to settle
-// it), a lane per query.  The cubes above know nothing of the best distance: radius 1 walks 27 cells, eight of them again,
-// and where it does not settle -- the sparse part of a cloud of mixed dimension: the points inside an object beside its
-// faces -- radius 2 walks 125, the 27 again.  A candidate at distance d makes everything beyond d irrelevant: only the
-// rows (y, z) whose slab lies within d of the query can matter, and in such a row only the cells within what is left of
-// d along x.  The rows of the box of cells around the ball, four at a time like the cubes; a row or a cell is passed
-// over by the rule that settles a query everywhere else in this file -- (its distance)^2 * kBoundSlack > best, the
-// distance to a rim cell measured as if the cell went on for ever outwards (it holds what was clamped into it) -- with
-// the best distance as it stands at that moment.  What is left when the rows are through is EXACT: no second stage.
-// A lane gives up (and is left to the stages after the cubes, with what it has found) if the box has more than
-// kBallMaxRows rows or four rows hold more than kLaneCubeMaxGroups groups.  aux: 1 settled, 2 gave up, 0 not active.
-constexpr int kBallMaxRows = 36;
-template <bool LAB, int W>
-__device__ __attribute__((noinline)) Found lane_ball_search(const GridSet g, const unsigned* __restrict__ cell_start,
-                                                            const pp::f4* __restrict__ sorted,
-                                                            const float* __restrict__ slab, float qx, float qy, float qz,
-                                                            float ql, bool active, float best_in, int bidx_in) {
-  const float px = (qx - g.minx) * g.invh, py = (qy - g.miny) * g.invh, pz = (qz - g.minz) * g.invh;  // in cells
-  const int cy = cell_coord(qy, g.miny, g.invh, g.gy), cz = cell_coord(qz, g.minz, g.invh, g.gz);
-  const float k2 = g.invh * g.invh / kBoundSlack;  // (distance in cells)^2 > best * k2: beyond the ball
-  float best = best_in;
-  int bidx = bidx_in;
-  // the box of rows: what the ball of the FIRST candidate reaches (cell_coord clamps: the rim rows stand for everything
-  // beyond them)
-  const float R = fast_sqrt(best_in * k2) * 1.00001f;
-  const bool box_ok = active && R <= kBallRmax;
-  // (from the query's position in cells, as the rows' distances below: (int) saturates, the clamp stands for the rim)
-  const int gy1 = g.gy - 1, gz1 = g.gz - 1;
-  int y0 = (int)(py - R), y1 = (int)(py + R), z0 = (int)(pz - R), z1 = (int)(pz + R);
-  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(y0) : "v"(y0), "v"(gy1));
-  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(y1) : "v"(y1), "v"(gy1));
-  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(z0) : "v"(z0), "v"(gz1));
-  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(z1) : "v"(z1), "v"(gz1));
-  y0 = min(y0, cy); y1 = max(y1, cy); z0 = min(z0, cz); z1 = max(z1, cz);
-  const int ny = y1 - y0 + 1;
-  int nrows = ny * (z1 - z0 + 1);
-  bool gave_up = active && (!box_ok || nrows > kBallMaxRows);
-  if (!active || gave_up) nrows = 0;
-  const float inv_ny = 1.0f / (float)ny;
-  const int gx1 = g.gx - 1;
-  // a row's span of the sorted cloud: empty when the row, or every cell of it, is beyond the ball as it stands
-  auto row_span = [&](int r) {
-    RowSpan o;
-    o.s = 0u;
-    o.e = 0u;
-    const int zi = (int)(((float)r + 0.5f) * inv_ny);
-    const int z = z0 + zi, y = y0 + (r - zi * ny);
-    const float dy = y < cy ? py - (float)(y + 1) : (y > cy ? (float)y - py : 0.0f);
-    const float dz = z < cz ? pz - (float)(z + 1) : (z > cz ? (float)z - pz : 0.0f);
-    const float w2 = best * k2 - (dy * dy + dz * dz);
-    if (r < nrows && w2 >= 0.0f) {
-      const float w = fast_sqrt(w2) * 1.00001f;
-      int x0 = (int)(px - w), x1 = (int)(px + w);  // (saturating conversions; NaN -> 0)
-      asm("v_med3_i32 %0, %1, 0, %2" : "=v"(x0) : "v"(x0), "v"(gx1));
-      asm("v_med3_i32 %0, %1, 0, %2" : "=v"(x1) : "v"(x1), "v"(gx1));
-      const int c = pp::cell_linear(0, y, z, g.gx, g.gy);
-      o.s = cell_start[c + x0];
-      o.e = cell_start[c + x1 + 1];
-    }
-    return o;
-  };
-  const int rmax = (int)pp::wave_reduce_dpp<false>((float)nrows);
-  for (int r0 = 0; r0 < rmax; r0 += 4) {  // wave-uniform
-    const RowSpan a0 = row_span(r0), a1 = row_span(r0 + 1), a2 = row_span(r0 + 2), a3 = row_span(r0 + 3);
-    unsigned t0 = (a0.e - a0.s + 3) >> 2, t1 = (a1.e - a1.s + 3) >> 2, t2 = (a2.e - a2.s + 3) >> 2,
-             t3 = (a3.e - a3.s + 3) >> 2;
-    if (t0 + t1 + t2 + t3 > (unsigned)kLaneCubeMaxGroups) {  // rows through a crowded region: the whole wave's work
-      gave_up = true;
-      nrows = 0;
-      t0 = t1 = t2 = t3 = 0u;
-    }
-    const unsigned T1 = t0, T2 = T1 + t1, T3 = T2 + t2, T4 = T3 + t3;
-    const unsigned adj0 = a0.s, adj1 = a1.s - 4 * T1, adj2 = a2.s - 4 * T2, adj3 = a3.s - 4 * T3;
-    const unsigned last0 = a0.e - 1, last1 = a1.e - 1, last2 = a2.e - 1, last3 = a3.e - 1;
-    pp::f4 pa[4], pb[4];
-    float la[4] = {0.0f, 0.0f, 0.0f, 0.0f}, lb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    stage_a_fetch<LAB>(0, T1, T2, T3, T4, adj0, adj1, adj2, adj3, last0, last1, last2, last3, sorted, slab, pa, la);
-    for (unsigned k = 0; __any(k < T4); k += 2) {
-      stage_a_fetch<LAB>(k + 1, T1, T2, T3, T4, adj0, adj1, adj2, adj3, last0, last1, last2, last3, sorted, slab, pb, lb);
-      if (k < T4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) take_candidate<LAB>(pa[u], la[u], qx, qy, qz, ql, best, bidx);
-      }
-      stage_a_fetch<LAB>(k + 2, T1, T2, T3, T4, adj0, adj1, adj2, adj3, last0, last1, last2, last3, sorted, slab, pa, la);
-      if (k + 1 < T4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) take_candidate<LAB>(pb[u], lb[u], qx, qy, qz, ql, best, bidx);
-      }
-    }
-  }
-  Found o;
-  o.best = active ? best : best_in;
-  o.bidx = active ? bidx : bidx_in;
-  o.aux = !active ? 0.0f : (gave_up ? 2.0f : 1.0f);
-  return o;
-}
-
-// Round 5 -- the same balls, POOLED over the wave.  A lane per query wastes the wave where few lanes
+// it).  The cubes know nothing of the best distance: radius 1 walks 27 cells, eight of them again, and where it does
+// not settle -- the sparse part of a cloud of mixed dimension: the points inside an object beside its faces -- radius 2
+// walks 125, the 27 again.  A candidate at distance d makes everything beyond d irrelevant: only the rows (y, z) whose
+// slab lies within d of the query can matter, and in such a row only the cells within what is left of d along x.  A row
+// or a cell is passed over by the rule that settles a query everywhere else in this file -- (its distance)^2 *
+// kBoundSlack > best, the distance to a rim cell measured as if the cell went on for ever outwards (it holds what was
+// clamped into it).  What is left when the rows are through is EXACT: no second stage.
+//
+// The balls are walked POOLED over the wave.  A lane per query wastes the wave where few lanes
 // are open (a tenth of a wave's queries in the sparse part of a cloud of mixed dimension) and every step waits for the
 // lane with the longest rows; here the open queries' work is laid out flat, twice:
 //   * the (query, row) pairs of every open query's box, 64 at a time: a lane works out ONE row's span inside the ball
@@ -1582,7 +1406,8 @@ __device__ __attribute__((noinline)) Found lane_ball_search(const GridSet g, con
 // of the marks and two popcounts give every lane its piece.  Every step is full width whatever the number of open
 // lanes, and the chain is two trips to memory for the whole wave instead of two per four rows of the slowest lane.
 // The ball is that of the candidate the query came with (it does not shrink on the way).  A row of more than
-// kPoolMaxGroups groups (a crowded region) makes its query give up (aux 2), as in the lane form.
+// kPoolMaxGroups groups (a crowded region) makes its query give up (aux 2) and leaves it, with what it has found, to
+// the stages after the cubes.
 // LDS (the wave's slice, free after stage A): see the offsets below; <= 6208 bytes (CAPW = 384).
 constexpr int kPoolItems = 256;       // pieces per flush
 constexpr int kPoolMaxGroups = 48;    // groups of a row before its query gives up
@@ -1595,7 +1420,7 @@ __device__ __attribute__((noinline)) Found wave_pooled_ball_search(const GridSet
                                                                    float qz, float ql, bool active, float best_in,
                                                                    int bidx_in, lds_f4_wptr slice, int rho) {
   // rho > 0 (wave-uniform): not the ball but the CUBE of Chebyshev radius rho around the query's cell, for the lanes that
-  // hold no candidate yet (lane_cube_search's job, pooled): every row of the cube, the cells cx - rho .. cx + rho of each;
+  // hold no candidate yet: every row of the cube, the cells cx - rho .. cx + rho of each;
   // settled (aux 1) if the best found lies below what the cube guarantees, else aux 0 with what was found.
   const int lane = threadIdx.x & 63;
   // ---- the slice, in bytes: queries (x, y, z, best * k2) | keys | boxes | first row of a query | pieces: start, first
@@ -1763,7 +1588,7 @@ __device__ __attribute__((noinline)) Found wave_pooled_ball_search(const GridSet
   o.best = active ? __uint_as_float((unsigned)(key >> 32)) : best_in;
   o.bidx = active ? (int)(unsigned)key : bidx_in;
   o.aux = !active ? 0.0f : (gave ? 2.0f : 1.0f);
-  if (rho > 0) {  // (uniform) what the cube guarantees: lane_cube_search's rule
+  if (rho > 0) {  // (uniform) what the cube guarantees
     const int cx = cell_coord(qx, g.minx, g.invh, g.gx);
     const float fx = (qx - g.minx) * g.invh - (float)cx, fy = py - (float)cy, fz = pz - (float)cz;
     auto axis = [&](float f, int c, int gdim) {
@@ -2195,8 +2020,8 @@ __device__ __forceinline__ void search_queries(const float* __restrict__ xyz1, c
     od[j] = best;
     oi[j] = bidx;
   }
-  // ---- what stage A left.  Many lanes of the wave (thin regions, the sparse scale of a two-scale cloud): the
-  // cubes of radius 1 and 2 a lane per query.  (Lanes next to a crowded cell stay with the whole-wave stages:
+  // ---- what stage A left (thin regions, the sparse scale of a two-scale cloud): the balls and the cubes of radius 1
+  // and 2, pooled over the wave.  (Lanes next to a crowded cell stay with the whole-wave stages:
   // a cube around them holds thousands of points.)
   bool pend = !resolved && valid;
   bool open_lane = false;
@@ -2210,21 +2035,16 @@ __device__ __forceinline__ void search_queries(const float* __restrict__ xyz1, c
     open_lane = true;
     pend = false;
   }
-  // (round 5) lanes that hold a candidate: the ball around it, exact in one stage (wave_pooled_ball_search / lane_ball_search);
+  // (round 5) lanes that hold a candidate: the ball around it, exact in one stage (wave_pooled_ball_search);
   // once for the candidates of the blocks, once more behind the cubes of radius 1 for the lanes those gave their first
   // candidate (an empty block in the sparse part of a cloud; labeled searches, where a block seldom holds the query's label)
-  bool ball_left = false;  // the ball gave up (rows through a crowded region): not for the lane cubes either
+  bool ball_left = false;  // the ball gave up (rows through a crowded region): not for the cubes either
   auto ball_stage = [&]() {
     // (a candidate further than kBallRmax cells: a box of rows larger than the cubes' -- those lanes stay with the cubes)
     const bool ball = pend && !deferred && !ball_left &&
                       best * (g.invh * g.invh) <= kBallRmax * kBallRmax * kBoundSlack * 0.9999f;
-    constexpr bool kPooled = CAPW >= 384;  // (the pooled form's lists need the slice of CAPW = 384)
-    if (__builtin_popcountll(__ballot(ball)) >= (kPooled ? kPoolMin : kBallMin)) {
-      Found f;
-      if constexpr (kPooled)
-        f = wave_pooled_ball_search<LAB, W>(g, cell_start, sorted, slab, qx, qy, qz, ql, ball, best, bidx, s_pts_w, 0);
-      else
-        f = lane_ball_search<LAB, W>(g, cell_start, sorted, slab, qx, qy, qz, ql, ball, best, bidx);
+    if (__builtin_popcountll(__ballot(ball)) >= kPoolMin) {
+      const Found f = wave_pooled_ball_search<LAB, W>(g, cell_start, sorted, slab, qx, qy, qz, ql, ball, best, bidx, s_pts_w, 0);
       best = f.best;
       bidx = f.bidx;
       if (f.aux == 1.0f) {
@@ -2237,16 +2057,11 @@ __device__ __forceinline__ void search_queries(const float* __restrict__ xyz1, c
   };
   ball_stage();
   // the cubes of radius 1 and 2 for the lanes without a candidate: pooled over the wave like the balls (from kPoolCubeMin
-  // lanes on), or a lane per query (from kLaneStageMin on)
-  constexpr bool kPooledCube = CAPW >= 384;
-  constexpr int kCubeMin = kPooledCube ? kPoolCubeMin : kLaneStageMin;
+  // lanes on)
   auto cube_stage = [&](int rho, bool mine) {
-    if constexpr (kPooledCube)
-      return wave_pooled_ball_search<LAB, W>(g, cell_start, sorted, slab, qx, qy, qz, ql, mine, best, bidx, s_pts_w, rho);
-    else
-      return lane_cube_search<LAB, W>(g, cell_start, sorted, slab, qx, qy, qz, ql, rho, mine, best, bidx);
+    return wave_pooled_ball_search<LAB, W>(g, cell_start, sorted, slab, qx, qy, qz, ql, mine, best, bidx, s_pts_w, rho);
   };
-  if (__builtin_popcountll(__ballot(pend && !deferred && !ball_left)) >= kCubeMin) {
+  if (__builtin_popcountll(__ballot(pend && !deferred && !ball_left)) >= kPoolCubeMin) {
     const bool mine = pend && !deferred && !ball_left;
     Found f = cube_stage(1, mine);
     best = f.best;
@@ -2265,7 +2080,7 @@ __device__ __forceinline__ void search_queries(const float* __restrict__ xyz1, c
     }
     ball_stage();
     const bool mine2 = pend && !deferred && !ball_left && f.aux != 2.0f;
-    if (__builtin_popcountll(__ballot(mine2)) >= kCubeMin) {
+    if (__builtin_popcountll(__ballot(mine2)) >= kPoolCubeMin) {
       f = cube_stage(2, mine2);
       best = f.best;
       bidx = f.bidx;

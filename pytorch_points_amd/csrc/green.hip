@@ -114,10 +114,6 @@ __device__ __forceinline__ Dual<K> operator+(double c, const Dual<K>& a) {
   return chain(a, c + a.v, 1.0);
 }
 template <int K>
-__device__ __forceinline__ Dual<K> operator-(const Dual<K>& a, double c) {
-  return chain(a, a.v - c, 1.0);
-}
-template <int K>
 __device__ __forceinline__ Dual<K> operator-(double c, const Dual<K>& a) {
   return chain(a, c - a.v, -1.0);
 }

@@ -27,11 +27,8 @@ constexpr int kMaxLds = 160 * 1024;         // LDS per workgroup on gfx950
 
 __device__ __forceinline__ float m_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double m_sqrt(double x) { return sqrt(x); }
-__device__ __forceinline__ float m_asin(float x) { return asinf(x); }
 __device__ __forceinline__ double m_asin(double x) { return asin(x); }
-__device__ __forceinline__ void m_sincos(float x, float* s, float* c) { sincosf(x, s, c); }
 __device__ __forceinline__ void m_sincos(double x, double* s, double* c) { sincos(x, s, c); }
-__device__ __forceinline__ float m_sin(float x) { return sinf(x); }
 __device__ __forceinline__ double m_sin(double x) { return sin(x); }
 __device__ __forceinline__ float m_nan(float) { return __builtin_nanf(""); }
 __device__ __forceinline__ double m_nan(double) { return __builtin_nan(""); }

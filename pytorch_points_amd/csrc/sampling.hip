@@ -460,7 +460,7 @@ __global__ __launch_bounds__(512, 4) void group_points_lds_kernel(const float* _
 // -- ; the stores alone, without any barrier, would take 0.75 ms).  Full chunks of 512 * 4 * V positions only.
 // ------------------------------------------------------------------------------------------------
 constexpr int kDma1Threads = 512;
-template <int V, bool NT = false>
+template <int V>
 __global__ __launch_bounds__(kDma1Threads) void group_points_dma1_kernel(const float* __restrict__ points,
                                                                          const int* __restrict__ idx,
                                                                          float* __restrict__ out, int B, int C,
@@ -507,17 +507,14 @@ __global__ __launch_bounds__(kDma1Threads) void group_points_dma1_kernel(const f
       r.y = s_row1[ii[v][1]];
       r.z = s_row1[ii[v][2]];
       r.w = s_row1[ii[v][3]];
-      if (NT)
-        __builtin_nontemporal_store(r, reinterpret_cast<pp::f4*>(o + p0 + (long long)v * (kDma1Threads * 4)));
-      else
-        *reinterpret_cast<pp::f4*>(o + p0 + (long long)v * (kDma1Threads * 4)) = r;
+      __builtin_nontemporal_store(r, reinterpret_cast<pp::f4*>(o + p0 + (long long)v * (kDma1Threads * 4)));
     }
     __builtin_amdgcn_s_barrier();  // every wave has read the row: the next one may land
     asm volatile("" ::: "memory");
   }
 }
 
-template <int V, bool NT = false>
+template <int V>
 bool launch_group_dma1(const float* points, const int* idx, float* out, int B, int C, int N, long long P,
                        long long obs, hipStream_t s) {
   const long long per_block = (long long)kDma1Threads * 4 * V;
@@ -533,8 +530,8 @@ bool launch_group_dma1(const float* points, const int* idx, float* out, int B, i
   const size_t lds = (size_t)passes * kDma1Threads * 16;
   if (lds > 72 * 1024 || chunks > 0x7fffffLL || blocks > 0x7fffffffLL) return false;
   static pp::DeviceFlags lds_ok;
-  if (pp::allow_big_lds(group_points_dma1_kernel<V, NT>, 80 * 1024, lds_ok) != hipSuccess) return false;  // (another kernel)
-  group_points_dma1_kernel<V, NT><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
+  if (pp::allow_big_lds(group_points_dma1_kernel<V>, 80 * 1024, lds_ok) != hipSuccess) return false;  // (another kernel)
+  group_points_dma1_kernel<V><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
       points, idx, out, B, C, N, P, (int)chunks, passes, cgroups, c_per_group, obs);
   return true;
 }
@@ -614,41 +611,6 @@ __global__ __launch_bounds__(256) void group_points_grad_kernel(const float* __r
   const int i = idx[(size_t)b * P + t];
   for (int c = c0; c < c1; ++c)
     atomicAdd(grad_points + ((size_t)b * C + c) * N + i, grad_out[(size_t)b * gbs + (size_t)c * P + t]);
-}
-
-// group_points backward without global atomics: one workgroup per (batch, channel) owns the column
-// grad_points[b,c,:] in LDS, streams grad_out[b,c,:,:] and idx[b,:,:] with 16-byte loads, adds with
-// ds_add_f32 and ADDS the column to the caller's (zero-filled) output once.  At config 4 the
-// reference's formulation is 1.07e9 scattered global atomics.  Workgroups of one batch element share
-// blockIdx % 8, so idx (re-read per channel) is served by one XCD's L2.
-__global__ __launch_bounds__(1024) void group_points_grad_lds_kernel(const float* __restrict__ grad_out,
-                                                                     const int* __restrict__ idx,
-                                                                     float* __restrict__ grad_points,
-                                                                     int B, int C, int N, long long P,
-                                                                     long long gbs) {
-  extern __shared__ __attribute__((aligned(16))) float s_col[];
-  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
-  const int b = x + 8 * (y / C);
-  const int c = y % C;
-  if (b >= B) return;
-  const int t = threadIdx.x;
-  for (int k = t; k < N; k += 1024) s_col[k] = 0.0f;
-  __syncthreads();
-  const float* __restrict__ go = grad_out + (size_t)b * gbs + (size_t)c * P;
-  const int* __restrict__ ib = idx + (size_t)b * P;
-  const long long p4 = P >> 2;
-  for (long long e = t; e < p4; e += 1024) {
-    const pp::f4 g = reinterpret_cast<const pp::f4*>(go)[e];
-    const pp::i4 i = reinterpret_cast<const pp::i4*>(ib)[e];
-    atomicAdd(&s_col[i.x], g.x);
-    atomicAdd(&s_col[i.y], g.y);
-    atomicAdd(&s_col[i.z], g.z);
-    atomicAdd(&s_col[i.w], g.w);
-  }
-  for (long long e = (p4 << 2) + t; e < P; e += 1024) atomicAdd(&s_col[ib[e]], go[e]);
-  __syncthreads();
-  float* __restrict__ gp = grad_points + ((size_t)b * C + c) * N;
-  for (int k = t; k < N; k += 1024) gp[k] += s_col[k];  // accumulate: the ABI's contract
 }
 
 // The same with a DOUBLE column: on gfx950 ds_add_f64 runs at 3.3 lanes/clk/CU against 0.36 for
@@ -1231,8 +1193,9 @@ int ball_query_scan_unusable(const float* new_xyz, const float* xyz, int* idx, i
 }
 }  // namespace pp
 
-// 0 = automatic; 1 = force the global-gather kernel; 2/4/8 = force the LDS-staged kernel with that
-// many index quads per thread (tests and tuning)
+// 0 = automatic; 1 = force the global-gather kernel; 2/4/8 = force the VGPR-staged LDS kernel with that many index
+// quads per thread; 604/608/616 = the LDS-DMA kernel with 4/8/16 quads where the positions fill whole chunks, the
+// VGPR-staged one elsewhere; any other value above 100 = no LDS-DMA kernel (tests and tuning)
 static pp::Knob g_group_variant;
 extern "C" void pp_debug_set_group_points_variant(int v) { g_group_variant.set(v); }
 
@@ -1261,17 +1224,17 @@ extern "C" int pp_group_points_strided_f32(const float* points, const int* idx, 
     bool ok = false;
     // the LDS-DMA form wherever the positions fill whole chunks (16, 8 or 4 index quads per thread): measured round 6
     // at or ahead of every other form on every shape it can take (tools/group_shapes_time.py); the output is written
-    // with non-temporal stores (4 GiB at config 4, nothing of it is read back from the caches; 516: ordinary stores)
+    // with non-temporal stores (4 GiB at config 4, nothing of it is read back from the caches)
     const int gv = g_group_variant;
-    if (gv == 516) ok = launch_group_dma1<16, false>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 616 || gv == 0)) ok = launch_group_dma1<16, true>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 608 || gv == 0)) ok = launch_group_dma1<8, true>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 604 || gv == 0)) ok = launch_group_dma1<4, true>(points, idx, out, B, C, N, P, obs, s);
+    if (gv == 616 || gv == 0) ok = launch_group_dma1<16>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok && (gv == 608 || gv == 0)) ok = launch_group_dma1<8>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok && (gv == 604 || gv == 0)) ok = launch_group_dma1<4>(points, idx, out, B, C, N, P, obs, s);
     if (ok) {
       PP_RETURN_IF_LAUNCH_FAILED();
       return PP_OK;
     }
-    // ragged chunks: the VGPR-staged form, 8 / 4 / 2 index quads per thread by the positions a CU gets
+    // ragged chunks: the VGPR-staged form, 8 / 4 / 2 index quads per thread by the positions a CU gets (> 100: the
+    // values 604 / 608 / 616 on shapes their LDS-DMA kernel cannot take)
     if (g_group_variant == 8 || ((g_group_variant == 0 || g_group_variant > 100) && per_cu >= 512LL * 4 * 8))
       ok = launch_group_lds<8>(points, idx, out, B, C, N, P, obs, s);
     else if (g_group_variant == 4 || (g_group_variant == 0 && per_cu >= 512LL * 4 * 4))
@@ -1315,8 +1278,8 @@ extern "C" int pp_group_points_strided_f32(const float* points, const int* idx, 
   return PP_OK;
 }
 
-// 0 = automatic; 1 = force global atomics; 2 = force the LDS-column form (double column when it
-// fits); 3 = force the LDS-column form with the fp32 column (tests and tuning)
+// 0 = automatic; 1 = force global atomics; 2 = the double LDS column also below 4096 positions; every other value
+// means 0 (tests and tuning)
 static pp::Knob g_group_grad_variant;
 extern "C" void pp_debug_set_group_points_grad_variant(int v) { g_group_grad_variant.set(v); }
 
@@ -1353,12 +1316,12 @@ static int group_points_grad_launch(const float* grad_out, const int* idx, float
   if (!grad_out || !idx || !grad_points || N == 0) return PP_EINVAL;
   // LDS-column forms: 16-byte aligned streams, enough work per column
   const bool vec = (uintptr_t)grad_out % 16 == 0 && (uintptr_t)idx % 16 == 0 && P % 4 == 0 && gbs % 4 == 0;
-  if (g_group_grad_variant != 1 && (vec || g_group_grad_variant != 3) &&
-      8LL * ((B + 7) / 8) * C <= 0x7fffffffLL && (g_group_grad_variant >= 2 || P >= 4096)) {
+  if (g_group_grad_variant != 1 && 8LL * ((B + 7) / 8) * C <= 0x7fffffffLL &&
+      (g_group_grad_variant == 2 || P >= 4096)) {
     constexpr int kW64 = 152 * 1024 / 8;  // destinations per workgroup with a double column
     const int nsplit = (N + kW64 - 1) / kW64;
     const long long wgs = 8LL * ((B + 7) / 8) * C * nsplit;
-    if (g_group_grad_variant != 3 && nsplit <= 16 && wgs <= 0x7fffffffLL) {
+    if (nsplit <= 16 && wgs <= 0x7fffffffLL) {
       const int W = nsplit == 1 ? N : kW64;
       static pp::DeviceFlags lds64_ok, lds64s_ok;
       if (vec) {
@@ -1377,23 +1340,8 @@ static int group_points_grad_launch(const float* grad_out, const int* idx, float
       PP_RETURN_IF_LAUNCH_FAILED();
       return PP_OK;
     }
-    if (overwrite) {  // (the forms below accumulate)
-      const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
-      if (e != PP_OK) return e;
-      overwrite = false;
-    }
-    if (vec && (size_t)N * sizeof(float) <= 160 * 1024) {  // fp32 column (kept for comparison: ds_add_f32 is slow)
-      static pp::DeviceFlags lds_ok;
-      const hipError_t e = pp::allow_big_lds(group_points_grad_lds_kernel, 160 * 1024, lds_ok);
-      if (e != hipSuccess) return (int)e;
-      group_points_grad_lds_kernel<<<dim3((unsigned)(8 * ((B + 7) / 8) * C)), dim3(1024),
-                                     (size_t)N * sizeof(float), (hipStream_t)stream>>>(
-          grad_out, idx, grad_points, B, C, N, P, gbs);
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
-    }
   }
-  if (overwrite) {
+  if (overwrite) {  // (global atomics accumulate)
     const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
     if (e != PP_OK) return e;
   }

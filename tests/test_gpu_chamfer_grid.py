@@ -443,10 +443,10 @@ def test_config2_class_clouds_equal_brute_force(cuda, name):
             assert same, "%s (launch %d): %s differs at %d places" % (name, rep, what, int((g != e).sum()))
 
 
-# ---- round 5: the balls behind stage A (lane_ball_search, wave_pooled_ball_search): clouds of mixed dimension -- thin
+# ---- round 5: the balls behind stage A (wave_pooled_ball_search): clouds of mixed dimension -- thin
 # faces with a sparse interior, where a query's block holds a candidate too far to settle it -- at several sizes, far
 # from the origin (the ball is measured in cells from the query's own cell coordinates), with outliers clamped into the
-# rim cells the balls reach, with ties; unlabeled (the pooled form) and labeled (the lane form): the every-pair kernel's
+# rim cells the balls reach, with ties; unlabeled and labeled (both pooled over the wave): the every-pair kernel's
 # outputs, bit for bit.
 def _object_like(seed, b, n, offset=0.0, scale=1.0):
     u = _u(seed, (b, n, 3)) - np.float32(0.5)

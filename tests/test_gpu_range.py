@@ -331,7 +331,7 @@ def test_group_and_gather_extreme_values(cuda, kind):
     x = R.pair("tiny_21", "lattice", n, 26)
     idx = oracle.ball_query(x[:, :npoint], x, 2.0 ** -69, ns)
     exp = oracle.group_points(feats, idx)
-    for v in (0, 1, 2, 4, 8, 516, 604):
+    for v in (0, 1, 2, 4, 8, 604):
         with knobs(group_points_variant=v):
             got = sampling.group_points(_t(feats, cuda), _t(idx, cuda))
             torch.cuda.synchronize()
@@ -345,7 +345,7 @@ def test_group_and_gather_extreme_values(cuda, kind):
             np.add.at(ex[k, j], idx[k].ravel(), go[k, j].ravel().astype(np.float64))
             np.add.at(ab[k, j], idx[k].ravel(), np.abs(go[k, j].ravel().astype(np.float64)))
         np.add.at(cnt[k, 0], idx[k].ravel(), 1)
-    for v in (0, 1, 2, 3):
+    for v in (0, 1, 2):
         with knobs(group_points_grad_variant=v):
             got = sampling.group_points_grad(_t(go, cuda), _t(idx, cuda), n)
             torch.cuda.synchronize()

@@ -15,7 +15,7 @@ smode.argtypes = [ctypes.c_int]; smode.restype = None
 smode(1)
 pats = {"ball r=0.10 (pads)": sampling.ball_query(c, x, 0.1, ns), "ball r=0.25 (full)": sampling.ball_query(c, x, 0.25, ns),
         "random": torch.randint(0, N, (B, M, ns), device=dev, dtype=torch.int32)}
-for v in [int(a) for a in sys.argv[1:]] or [2, 3]:
+for v in [int(a) for a in sys.argv[1:]] or [2]:
     var(v)
     for name, idx in pats.items():
         for _ in range(2): sampling.group_points_grad(go, idx, N)
