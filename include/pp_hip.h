@@ -283,6 +283,50 @@ int pp_three_interpolate_grad_ordered_f32(const float* grad_out, const int* idx,
                                           float* grad_points, int B, int C, int N, int M, void* workspace,
                                           size_t workspace_bytes, void* stream);
 
+/* ---- 16-bit features (DESIGN.md §4 "16-bit features") --------------------------------------------
+ * gather_points, group_points and three_interpolate on FEATURE tensors of IEEE half (_f16) or bfloat16 (_bf16)
+ * elements; idx stays int32 and weight fp32.  Shapes and argument order as the _f32 entry points.
+ *   _b16: a copy -- the gathered 2-byte words are moved unchanged (every NaN payload, both zeros, subnormals), so
+ *     one entry point serves both types.  out_batch_stride is in elements.
+ *   pp_three_interpolate_f16/_bf16: the operands widened (exact), the fp32 chain fma(w2,p2, fma(w0,p0, w1*p1)), one
+ *     rounding to nearest even (half overflows to +-inf): bit-identical to rounding the _f32 result on the widened
+ *     features.
+ *   *_out_ws_f16/_bf16: the backwards.  grad_points is WRITTEN (no zero fill by the caller, the output is not read).
+ *     Each destination's terms -- the widened grad_out, for three_interpolate the fp32 products with the weight -- are
+ *     summed in the accumulator of the fp32 form (the double LDS column, or the fp32 slots of the sorted scatter) and
+ *     rounded once: double -> float -> T, or float -> T.  No 16-bit floating-point atomics: PP_ENOTSUP when no
+ *     atomic-free form serves the shape (no sorted-scatter workspace qualifies, e.g. more than 20480 destinations, and
+ *     the double column does not apply: group_points below 4096 positions, three_interpolate below 2048 points or
+ *     beyond 19456 known points; gather has the sorted form only) -- the caller then widens and uses the _f32 path.
+ *     The deterministic mode is the `ordered` ARGUMENT (not separate symbols: it halves these declarations):
+ *     ordered != 0 takes the sorted scatter in ascending source order -- the rounded result of the *_ordered_f32
+ *     entry point, bit for bit -- or returns PP_ENOTSUP.  workspace: pp_scatter_workspace_bytes, as for _f32 (the
+ *     triple lists do not depend on the element type).
+ * Sizes of zero are served, a negative size returns PP_EINVAL, both before any pointer is looked at. */
+int pp_gather_forward_b16(const void* points, const int* idx, void* out, int B, int C, int N, int M, void* stream);
+int pp_group_points_strided_b16(const void* points, const int* idx, void* out, int B, int C, int N, int npoint,
+                                int nsample, long long out_batch_stride, void* stream);
+int pp_three_interpolate_f16(const void* points, const int* idx, const float* weight, void* out, int B, int C, int M,
+                             int N, void* stream);
+int pp_three_interpolate_bf16(const void* points, const int* idx, const float* weight, void* out, int B, int C, int M,
+                              int N, void* stream);
+int pp_gather_backward_out_ws_f16(const void* grad_out, const int* idx, void* grad_points, int B, int C, int N, int M,
+                                  void* workspace, size_t workspace_bytes, int ordered, void* stream);
+int pp_gather_backward_out_ws_bf16(const void* grad_out, const int* idx, void* grad_points, int B, int C, int N, int M,
+                                   void* workspace, size_t workspace_bytes, int ordered, void* stream);
+int pp_group_points_grad_out_ws_f16(const void* grad_out, const int* idx, void* grad_points, int B, int C, int N,
+                                    int npoint, int nsample, long long grad_out_batch_stride, void* workspace,
+                                    size_t workspace_bytes, int ordered, void* stream);
+int pp_group_points_grad_out_ws_bf16(const void* grad_out, const int* idx, void* grad_points, int B, int C, int N,
+                                     int npoint, int nsample, long long grad_out_batch_stride, void* workspace,
+                                     size_t workspace_bytes, int ordered, void* stream);
+int pp_three_interpolate_grad_out_ws_f16(const void* grad_out, const int* idx, const float* weight, void* grad_points,
+                                         int B, int C, int N, int M, void* workspace, size_t workspace_bytes,
+                                         int ordered, void* stream);
+int pp_three_interpolate_grad_out_ws_bf16(const void* grad_out, const int* idx, const float* weight, void* grad_points,
+                                          int B, int C, int N, int M, void* workspace, size_t workspace_bytes,
+                                          int ordered, void* stream);
+
 /* ---- _ext.linalg ------------------------------------------------------------------------
  * Replaces linalg.batch_svd_forward(a, is_sort, tol, max_sweeps) (torch_batch_svd.cpp:38-140, cuSOLVER gesvdj).
  * a (batch,m,n), m,n in 1..32 -> a = U[:, :, :k] diag(s) V[:, :, :k]^T, k = min(m,n); s (batch,k) >= 0;

@@ -61,18 +61,26 @@ void pp_debug_set_fps_bucket_chain(int form);
 /* the bucketed FPS kernel's sort: 0 = by the whole chip from 32768 points (six short launches in front of the kernel),
  * below that inside the kernel by its one workgroup; 1 = always inside the kernel */
 void pp_debug_set_fps_bucket_sort(int mode);
+/* gather_points forward: 0 automatic, 1 the global-gather kernel; 2 = the 16-bit dispatch (pp_gather_forward_b16) takes
+ * its LDS form wherever the row fits (the fp32 dispatch reads 2 as 0) */
 void pp_debug_set_gather_variant(int variant);
 void pp_debug_set_ball_query_variant(int variant); /* scan kernels: 1 = one wave per 64 centres */
 void pp_debug_set_ball_query_search(int mode);     /* 0 automatic, 1 scan, 2 grid wherever possible */
 void pp_debug_set_ball_query_lpc(int lanes_per_centre);
 /* group_points: 0 automatic, 1 the global-gather kernel, 2 / 4 / 8 the VGPR-staged LDS kernel with that many index
  * quads per thread, 604 / 608 / 616 the LDS-DMA kernel with 4 / 8 / 16 quads where the positions fill whole chunks (the
- * VGPR-staged one elsewhere); any other value above 100: no LDS-DMA kernel */
+ * VGPR-staged one elsewhere); any other value above 100: no LDS-DMA kernel.  The 16-bit dispatch
+ * (pp_group_points_strided_b16) reads the same values: 604 / 608 / 616 its LDS-DMA kernel with 2 / 4 / 8 index OCTETS
+ * (the same chunks of positions), 2 / 4 / 8 and the other values above 100 its one register-staged LDS kernel; a value
+ * that names an LDS form takes it below the automatic choice's 256 * 2048 positions as well (aligned shapes only) */
 void pp_debug_set_group_points_variant(int variant);
 /* group_points_grad: 0 automatic, 1 global atomics, 2 the double LDS column also below 4096 positions; any other
  * value means 0 */
 void pp_debug_set_group_points_grad_variant(int variant);
 void pp_debug_set_three_nn_search(int mode);       /* 0 automatic, 1 scan */
+/* three_interpolate: 0 automatic, 1 the global-gather kernel, 2 no channel-group form (fp32: the row-at-a-time LDS form
+ * where it applies; 16-bit: the global form); 3 = the 16-bit dispatch takes its channel-group form wherever the rows
+ * fit (the fp32 dispatch reads 3 as 0).  The *_grad_* knobs and the scatter mode mean the same to both dispatches */
 void pp_debug_set_three_interpolate_variant(int variant);
 void pp_debug_set_three_interpolate_grad_variant(int variant);
 void pp_debug_set_scatter_mode(int mode);          /* 1 = never use the sorted scatter-add form */

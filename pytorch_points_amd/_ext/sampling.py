@@ -141,26 +141,44 @@ def furthest_sampling(m, seedIdx, input, temp, idx, sampled=None, channels_first
     return idx
 
 
+# --- 16-bit features: float16 / bfloat16 FEATURE tensors go to the *_b16 (copies) and *_f16 / *_bf16
+# --- (arithmetic, backwards) entry points; coordinates, weights and indices keep their types --------------------------
+_SUFFIX16 = {torch.float16: "f16", torch.bfloat16: "bf16"}
+
+
+def _entry16(stem, dtype):
+    return getattr(_lib.lib(), "%s_%s" % (stem, _SUFFIX16[dtype]))
+
+
+def _served16(code, what):
+    """outcome of a 16-bit backward entry point: True = done; False = PP_ENOTSUP, no atomic-free form serves the shape
+    (the caller widens grad_out, runs the fp32 path and rounds); raises otherwise"""
+    if code == _lib.PP_ENOTSUP:
+        return False
+    _lib.check(code, what)
+    return True
+
+
 def gather_forward(b, c, n, npoints, points, idx, out):
     """gather_points_wrapper_fast (sampling.cpp:19-28): out[b,c,m] = points[b,c,idx[b,m]]"""
     dev = _lib.require_cuda(("points", points), ("idx", idx), ("out", out))
     _lib.require_contiguous(("points", points), ("idx", idx), ("out", out))
-    _lib.require_float(("points", points), ("out", out))
+    dt = _lib.require_feature_dtype(("points", points), ("out", out))
     _lib.require_int(("idx", idx))
     if points.numel() != b * c * n or idx.numel() != b * npoints or out.numel() != b * c * npoints:
         raise RuntimeError("gather_forward: tensor sizes do not match (b, c, n, npoints)")
     with _lib.on_device(dev) as stream:
-        _lib.check(_lib.lib().pp_gather_forward_f32(
-            _lib.ptr(points), _lib.ptr(idx), _lib.ptr(out), b, c, n, npoints, stream),
-            "gather_forward")
+        fn = _lib.lib().pp_gather_forward_f32 if dt is torch.float32 else _lib.lib().pp_gather_forward_b16
+        _lib.check(fn(_lib.ptr(points), _lib.ptr(idx), _lib.ptr(out), b, c, n, npoints, stream), "gather_forward")
     return 1
 
 
 def gather_backward(b, c, n, npoints, grad_out, idx, grad_points):
-    """gather_points_grad_wrapper_fast (sampling.cpp:31-41): scatter-add into grad_points."""
+    """gather_points_grad_wrapper_fast (sampling.cpp:31-41): scatter-add into grad_points.  16-bit tensors:
+    grad_points is WRITTEN (it need not be initialised)."""
     dev = _lib.require_cuda(("grad_out", grad_out), ("idx", idx), ("grad_points", grad_points))
     _lib.require_contiguous(("grad_out", grad_out), ("idx", idx), ("grad_points", grad_points))
-    _lib.require_float(("grad_out", grad_out), ("grad_points", grad_points))
+    dt = _lib.require_feature_dtype(("grad_out", grad_out), ("grad_points", grad_points))
     _lib.require_int(("idx", idx))
     if (grad_out.numel() != b * c * npoints or idx.numel() != b * npoints
             or grad_points.numel() != b * c * n):
@@ -170,6 +188,13 @@ def gather_backward(b, c, n, npoints, grad_out, idx, grad_points):
         args = (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad_points), b, c, n, npoints,
                 _lib.ptr(ws) if ws is not None else None, nbytes, stream)
         L = _lib.lib()
+        if dt is not torch.float32:
+            ordered = 1 if _lib.deterministic() else 0
+            if not _served16(_entry16("pp_gather_backward_out_ws", dt)(*args[:-1], ordered, stream), "gather_backward"):
+                wide = torch.zeros(grad_points.shape, dtype=torch.float32, device=dev)
+                gather_backward(b, c, n, npoints, grad_out.float(), idx, wide)
+                grad_points.copy_(wide)
+            return 1
         if not (_lib.deterministic() and _lib.ordered_or_fallback(L.pp_gather_backward_ordered_f32(*args), "gather_backward")):
             _lib.check(L.pp_gather_backward_ws_f32(*args), "gather_backward")
     return 1
@@ -206,7 +231,7 @@ def group_points(points, idx):
     """group_points (sampling.cpp:113-138): points (B,C,N), idx (B,npoint,nsample) ->
     (B,C,npoint,nsample)."""
     _lib.require_contiguous(("points", points), ("idx", idx))
-    _lib.require_float(("points", points))
+    dt = _lib.require_feature_dtype(("points", points))
     _lib.require_int(("idx", idx))
     if not points.is_cuda:
         raise RuntimeError("CPU not supported")  # sampling.cpp:132
@@ -215,18 +240,22 @@ def group_points(points, idx):
         raise RuntimeError("points must be (B, C, N) and idx (B, npoint, nsample)")
     b, c, n = points.shape
     _, npoint, nsample = idx.shape
-    out = torch.empty(b, c, npoint, nsample, dtype=torch.float32, device=dev)  # fully written
+    out = torch.empty(b, c, npoint, nsample, dtype=dt, device=dev)  # fully written
     with _lib.on_device(dev) as stream:
-        _lib.check(_lib.lib().pp_group_points_f32(
-            _lib.ptr(points), _lib.ptr(idx), _lib.ptr(out), b, c, n, npoint, nsample, stream),
-            "group_points")
+        if dt is torch.float32:
+            code = _lib.lib().pp_group_points_f32(
+                _lib.ptr(points), _lib.ptr(idx), _lib.ptr(out), b, c, n, npoint, nsample, stream)
+        else:
+            code = _lib.lib().pp_group_points_strided_b16(
+                _lib.ptr(points), _lib.ptr(idx), _lib.ptr(out), b, c, n, npoint, nsample, c * npoint * nsample, stream)
+        _lib.check(code, "group_points")
     return out
 
 
 def group_points_grad(grad_out, idx, n):
     """group_points_grad (sampling.cpp:140-161): grad_out (B,C,npoint,nsample) -> (B,C,n)."""
     _lib.require_contiguous(("grad_out", grad_out), ("idx", idx))
-    _lib.require_float(("grad_out", grad_out))
+    dt = _lib.require_feature_dtype(("grad_out", grad_out))
     _lib.require_int(("idx", idx))
     if not grad_out.is_cuda:
         raise RuntimeError("CPU not supported")  # sampling.cpp:157
@@ -237,6 +266,16 @@ def group_points_grad(grad_out, idx, n):
     # (the deterministic form accumulates into zeros, as the reference's does; the default form WRITES every element:
     #  no fill in front of it, no read of the output -- pp_group_points_grad_out_ws_f32)
     det = _lib.deterministic()
+    if dt is not torch.float32:   # (the 16-bit entry points write every element in both modes)
+        out = torch.empty(b, c, int(n), dtype=dt, device=dev)
+        with _lib.on_device(dev) as stream:
+            ws, nbytes = _scatter_ws(dev, b, npoint * nsample, int(n), 1, 0)
+            code = _entry16("pp_group_points_grad_out_ws", dt)(
+                _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(out), b, c, int(n), npoint, nsample, c * npoint * nsample,
+                _lib.ptr(ws) if ws is not None else None, nbytes, 1 if det else 0, stream)
+        if not _served16(code, "group_points_grad"):
+            return group_points_grad(grad_out.float(), idx, n).to(dt)
+        return out
     out = (torch.zeros if det else torch.empty)(b, c, int(n), dtype=torch.float32, device=dev)
     with _lib.on_device(dev) as stream:
         ws, nbytes = _scatter_ws(dev, b, npoint * nsample, int(n), 1, 0)
@@ -254,7 +293,7 @@ def group_points_into(points, idx, out, channel_offset):
     """out[:, channel_offset : channel_offset + C] = group_points(points, idx), written in place.
     points (B,C,N), idx (B,npoint,nsample), out (B,Ctot,npoint,nsample) contiguous."""
     _lib.require_contiguous(("points", points), ("idx", idx), ("out", out))
-    _lib.require_float(("points", points), ("out", out))
+    dt = _lib.require_feature_dtype(("points", points), ("out", out))
     _lib.require_int(("idx", idx))
     dev = _lib.require_cuda(("points", points), ("idx", idx), ("out", out))
     b, c, n = points.shape
@@ -264,8 +303,9 @@ def group_points_into(points, idx, out, channel_offset):
         raise RuntimeError("out must be (B, Ctot, npoint, nsample) with room for C channels at channel_offset")
     p = npoint * nsample
     with _lib.on_device(dev) as stream:
-        _lib.check(_lib.lib().pp_group_points_strided_f32(
-            _lib.ptr(points), _lib.ptr(idx), _lib._c_void_p(out.data_ptr() + 4 * channel_offset * p),
+        fn = _lib.lib().pp_group_points_strided_f32 if dt is torch.float32 else _lib.lib().pp_group_points_strided_b16
+        _lib.check(fn(
+            _lib.ptr(points), _lib.ptr(idx), _lib._c_void_p(out.data_ptr() + out.element_size() * channel_offset * p),
             b, c, n, npoint, nsample, out.size(1) * p, stream), "group_points_into")
     return out
 
@@ -274,7 +314,7 @@ def group_points_grad_from(grad_out, idx, n, channel_offset, channels):
     """group_points_grad of grad_out[:, channel_offset : channel_offset + channels] -> (B,channels,n),
     without materialising the slice.  grad_out (B,Ctot,npoint,nsample) contiguous."""
     _lib.require_contiguous(("grad_out", grad_out), ("idx", idx))
-    _lib.require_float(("grad_out", grad_out))
+    dt = _lib.require_feature_dtype(("grad_out", grad_out))
     _lib.require_int(("idx", idx))
     dev = _lib.require_cuda(("grad_out", grad_out), ("idx", idx))
     b, ctot, npoint, nsample = grad_out.shape
@@ -282,6 +322,18 @@ def group_points_grad_from(grad_out, idx, n, channel_offset, channels):
         raise RuntimeError("channel slice out of range")
     p = npoint * nsample
     det = _lib.deterministic()
+    if dt is not torch.float32:
+        out = torch.empty(b, channels, int(n), dtype=dt, device=dev)
+        with _lib.on_device(dev) as stream:
+            ws, nbytes = _scatter_ws(dev, b, p, int(n), 1, 0)
+            code = _entry16("pp_group_points_grad_out_ws", dt)(
+                _lib._c_void_p(grad_out.data_ptr() + 2 * channel_offset * p), _lib.ptr(idx), _lib.ptr(out), b, channels,
+                int(n), npoint, nsample, ctot * p, _lib.ptr(ws) if ws is not None else None, nbytes, 1 if det else 0,
+                stream)
+        if not _served16(code, "group_points_grad_from"):
+            part = grad_out[:, channel_offset:channel_offset + channels].float()   # (the slice alone is widened)
+            return group_points_grad(part, idx, n).to(dt)
+        return out
     out = (torch.zeros if det else torch.empty)(b, channels, int(n), dtype=torch.float32, device=dev)
     with _lib.on_device(dev) as stream:
         ws, nbytes = _scatter_ws(dev, b, p, int(n), 1, 0)
@@ -317,24 +369,26 @@ def three_interpolate_wrapper(b, c, m, n, points, idx, weight, out):
     floats = (("points", points), ("weight", weight), ("out", out))
     dev = _lib.require_cuda(*floats, ("idx", idx))
     _lib.require_contiguous(*floats, ("idx", idx))
-    _lib.require_float(*floats)
+    dt = _lib.require_feature_dtype(("points", points), ("out", out))
+    _lib.require_float(("weight", weight))
     _lib.require_int(("idx", idx))
     if points.numel() != b * c * m or idx.numel() != b * n * 3 or weight.numel() != b * n * 3 \
             or out.numel() != b * c * n:
         raise RuntimeError("three_interpolate_wrapper: tensor sizes do not match (b, c, m, n)")
     with _lib.on_device(dev) as stream:
-        _lib.check(_lib.lib().pp_three_interpolate_f32(
-            _lib.ptr(points), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(out), b, c, m, n, stream),
-            "three_interpolate_wrapper")
+        fn = _lib.lib().pp_three_interpolate_f32 if dt is torch.float32 else _entry16("pp_three_interpolate", dt)
+        _lib.check(fn(_lib.ptr(points), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(out), b, c, m, n, stream),
+                   "three_interpolate_wrapper")
 
 
 def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_points):
     """three_interpolate_grad_wrapper_fast (sampling.cpp:190-203): scatter-add into grad_points
-    (B,C,M)."""
+    (B,C,M).  16-bit tensors: grad_points is WRITTEN (it need not be initialised)."""
     floats = (("grad_out", grad_out), ("weight", weight), ("grad_points", grad_points))
     dev = _lib.require_cuda(*floats, ("idx", idx))
     _lib.require_contiguous(*floats, ("idx", idx))
-    _lib.require_float(*floats)
+    dt = _lib.require_feature_dtype(("grad_out", grad_out), ("grad_points", grad_points))
+    _lib.require_float(("weight", weight))
     _lib.require_int(("idx", idx))
     if grad_out.numel() != b * c * n or idx.numel() != b * n * 3 or weight.numel() != b * n * 3 \
             or grad_points.numel() != b * c * m:
@@ -344,6 +398,14 @@ def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_point
         args = (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_points), b, c, n, m,
                 _lib.ptr(ws) if ws is not None else None, nbytes, stream)
         L = _lib.lib()
+        if dt is not torch.float32:
+            ordered = 1 if _lib.deterministic() else 0
+            if not _served16(_entry16("pp_three_interpolate_grad_out_ws", dt)(*args[:-1], ordered, stream),
+                             "three_interpolate_grad_wrapper"):
+                wide = torch.zeros(grad_points.shape, dtype=torch.float32, device=dev)
+                three_interpolate_grad_wrapper(b, c, n, m, grad_out.float(), idx, weight, wide)
+                grad_points.copy_(wide)
+            return
         if not (_lib.deterministic() and _lib.ordered_or_fallback(L.pp_three_interpolate_grad_ordered_f32(*args),
                                                                   "three_interpolate_grad")):
             _lib.check(L.pp_three_interpolate_grad_ws_f32(*args), "three_interpolate_grad_wrapper")

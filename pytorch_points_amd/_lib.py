@@ -62,6 +62,16 @@ SIGNATURES = {
     "pp_group_points_grad_ordered_f32": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, _P, _c_size_t, _P],
     "pp_gather_backward_ordered_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _P],
     "pp_three_interpolate_grad_ordered_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_gather_forward_b16": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_group_points_strided_b16": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, _P],
+    "pp_three_interpolate_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_three_interpolate_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_gather_backward_out_ws_f16": [_P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _I, _P],
+    "pp_gather_backward_out_ws_bf16": [_P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _I, _P],
+    "pp_group_points_grad_out_ws_f16": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, _P, _c_size_t, _I, _P],
+    "pp_group_points_grad_out_ws_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, _P, _c_size_t, _I, _P],
+    "pp_three_interpolate_grad_out_ws_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _I, _P],
+    "pp_three_interpolate_grad_out_ws_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _c_size_t, _I, _P],
     "pp_three_nn_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
     "pp_three_interpolate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "pp_three_interpolate_grad_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -221,6 +231,23 @@ def require_float(*named):
     for name, t in named:
         if t.dtype != torch.float32:
             raise RuntimeError("%s must be a float tensor" % name)
+
+
+_FEATURE_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def require_feature_dtype(*named):
+    """The dtype rule of the FEATURE tensors of gather_points, group_points and three_interpolate (DESIGN.md §4 "16-bit
+    features"): float32, float16 or bfloat16, one common type per call; anything else (float64 among it) raises as
+    require_float does.  Coordinates, weights and distances stay with require_float.  -> the common dtype"""
+    dt = named[0][1].dtype
+    for name, t in named:
+        if t.dtype not in _FEATURE_DTYPES:
+            raise RuntimeError("%s must be a float tensor" % name)
+        if t.dtype != dt:
+            raise RuntimeError("%s is %s but %s is %s: the feature tensors of one call share one dtype"
+                               % (name, t.dtype, named[0][0], dt))
+    return dt
 
 
 def require_float_or_double(*named):

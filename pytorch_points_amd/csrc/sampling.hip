@@ -2,10 +2,16 @@
 // Replaces the reference's _ext/sampling_cuda.cu (gather :9-84, ball_query :340-397,
 // group_points :447-513) and _ext/interpolate_gpu.cu (three_nn :9-74, three_interpolate :77-160).
 #include "grid_common.h"
+#include "pp_b16.h"
 
 namespace pp {  // scatter.hip
 size_t ssa_workspace_bytes(int B, long long P, int R, int Nd, bool weighted);
 int ssa_run(const float* src, const int* dst, const float* weight, float* out, int B, int C,
+            long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered);
+// 16-bit sources (DESIGN.md §4 "16-bit features"): the same triples, `out` WRITTEN and rounded once
+int ssa_run(const f16* src, const int* dst, const float* weight, f16* out, int B, int C,
+            long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered);
+int ssa_run(const bf16* src, const int* dst, const float* weight, bf16* out, int B, int C,
             long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered);
 }  // namespace pp
 
@@ -17,9 +23,10 @@ using pp::dist3;
 // gather_points: out[b,c,m] = points[b,c,idx[b,m]]            (ref sampling_cuda.cu:9-25)
 // One thread per (b, m) column quad walks all channels: idx is read once, stores are contiguous.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gather_fwd_kernel(const float* __restrict__ points,
+template <typename E>  // float, or any 2-byte element as uint16_t (a copy moves bits)
+__global__ __launch_bounds__(256) void gather_fwd_kernel(const E* __restrict__ points,
                                                          const int* __restrict__ idx,
-                                                         float* __restrict__ out, int C, int N,
+                                                         E* __restrict__ out, int C, int N,
                                                          int M, int c_per_block) {
   const int b = blockIdx.z;
   const int m = blockIdx.x * 256 + threadIdx.x;
@@ -619,10 +626,29 @@ __global__ __launch_bounds__(256) void group_points_grad_kernel(const float* __r
 // destinations (8 W bytes of LDS) of one (batch, channel): the whole column when N fits, otherwise
 // one of `nsplit` ranges, each workgroup streaming the column's grad_out and skipping the entries
 // of the other ranges.  U 16-byte load pairs are in flight per thread before the first atomic.
-template <int U, bool VEC = true>
-__global__ __launch_bounds__(1024) void group_points_grad_lds64_kernel(const float* __restrict__ grad_out,
+// T = f16 / bf16 (DESIGN.md §4 "16-bit features"): the quad structure stays -- an 8-byte grad_out load beside the
+// 16-byte index load, widened in registers -- and the column is written as T(float(sum)); always `overwrite`.
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
+template <typename T>
+__device__ __forceinline__ pp::f4 widen_quad(const u2v w) {
+  T a[4];
+  __builtin_memcpy(a, &w, 8);
+  return pp::f4{pp::widen(a[0]), pp::widen(a[1]), pp::widen(a[2]), pp::widen(a[3])};
+}
+template <typename T, bool NT>
+__device__ __forceinline__ pp::f4 load_quad(const T* __restrict__ base, long long q) {
+  if constexpr (std::is_same<T, float>::value) {
+    const pp::f4* p = reinterpret_cast<const pp::f4*>(base) + q;
+    return NT ? __builtin_nontemporal_load(p) : *p;
+  } else {
+    const u2v* p = reinterpret_cast<const u2v*>(base) + q;
+    return widen_quad<T>(NT ? __builtin_nontemporal_load(p) : *p);
+  }
+}
+template <int U, bool VEC = true, typename T = float>
+__global__ __launch_bounds__(1024) void group_points_grad_lds64_kernel(const T* __restrict__ grad_out,
                                                                        const int* __restrict__ idx,
-                                                                       float* __restrict__ grad_points,
+                                                                       T* __restrict__ grad_points,
                                                                        int B, int C, int N, long long P,
                                                                        long long gbs, int nsplit, int W, int overwrite) {
   extern __shared__ __attribute__((aligned(16))) double s_col64[];
@@ -637,7 +663,7 @@ __global__ __launch_bounds__(1024) void group_points_grad_lds64_kernel(const flo
   const int t = threadIdx.x;
   for (int k = t; k < w; k += 1024) s_col64[k] = 0.0;
   __syncthreads();
-  const float* __restrict__ go = grad_out + (size_t)b * gbs + (size_t)c * P;
+  const T* __restrict__ go = grad_out + (size_t)b * gbs + (size_t)c * P;
   const int* __restrict__ ib = idx + (size_t)b * P;
   const long long p4 = P >> 2;
   auto add1 = [&](int i, double v) {
@@ -730,14 +756,14 @@ __global__ __launch_bounds__(1024) void group_points_grad_lds64_kernel(const flo
       for (int u = 0; u < U; ++u) {
         // (grad_out is read once: non-temporal, so that the 4 GiB stream does not push the indices -- re-read by
         //  every channel's workgroup -- out of the XCD's L2)
-        g[u] = __builtin_nontemporal_load(reinterpret_cast<const pp::f4*>(go) + e + 1024 * u);
+        g[u] = load_quad<T, true>(go, e + 1024 * u);
         i[u] = reinterpret_cast<const pp::i4*>(ib)[e + 1024 * u];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) add4_merged(g[u], i[u]);  // (every lane is active here: the DPP shifts see whole rows)
     }
-    for (; e < p4; e += 1024) add4(reinterpret_cast<const pp::f4*>(go)[e], reinterpret_cast<const pp::i4*>(ib)[e]);
-    for (long long q = (p4 << 2) + t; q < P; q += 1024) add1(ib[q], (double)go[q]);
+    for (; e < p4; e += 1024) add4(load_quad<T, false>(go, e), reinterpret_cast<const pp::i4*>(ib)[e]);
+    for (long long q = (p4 << 2) + t; q < P; q += 1024) add1(ib[q], (double)pp::widen(go[q]));
   } else {
     // rows that are not 16-byte aligned (P or the batch stride not a multiple of 4): 4-byte loads, still
     // coalesced, 2U in flight per thread -- slower than the vector form, far from the global-atomic one
@@ -747,17 +773,19 @@ __global__ __launch_bounds__(1024) void group_points_grad_lds64_kernel(const flo
       int i[2 * U];
 #pragma unroll
       for (int u = 0; u < 2 * U; ++u) {
-        g[u] = go[e + 1024 * u];
+        g[u] = pp::widen(go[e + 1024 * u]);
         i[u] = ib[e + 1024 * u];
       }
 #pragma unroll
       for (int u = 0; u < 2 * U; ++u) add1(i[u], (double)g[u]);
     }
-    for (; e < P; e += 1024) add1(ib[e], (double)go[e]);
+    for (; e < P; e += 1024) add1(ib[e], (double)pp::widen(go[e]));
   }
   __syncthreads();
-  float* __restrict__ gp = grad_points + ((size_t)b * C + c) * N + lo;
-  if (overwrite) {  // (uniform) pp_group_points_grad_out_*: every element is written once, nothing is read
+  T* __restrict__ gp = grad_points + ((size_t)b * C + c) * N + lo;
+  if constexpr (!std::is_same<T, float>::value) {  // double -> float -> T: R_T of the fp32 operator's result
+    for (int k = t; k < w; k += 1024) gp[k] = pp::narrow<T>((float)s_col64[k]);
+  } else if (overwrite) {  // (uniform) pp_group_points_grad_out_*: every element is written once, nothing is read
     for (int k = t; k < w; k += 1024) gp[k] = (float)s_col64[k];
   } else {
     for (int k = t; k < w; k += 1024) gp[k] += (float)s_col64[k];  // accumulate: the reference ABI's contract
@@ -809,10 +837,11 @@ __global__ __launch_bounds__(256) void three_nn_kernel(const float* __restrict__
 // three_interpolate (ref interpolate_gpu.cu:77-97): out[b,c,n] = w0*p[i0] + w1*p[i1] + w2*p[i2],
 // canonical rounding fma(w2,p2, fma(w0,p0, w1*p1)).  A thread keeps (idx, weight) of one n and
 // walks a slab of channels.
-__global__ __launch_bounds__(256) void three_interpolate_kernel(const float* __restrict__ points,
+template <typename T>  // 16-bit T: widened operands, the same fp32 chain, one rounding
+__global__ __launch_bounds__(256) void three_interpolate_kernel(const T* __restrict__ points,
                                                                 const int* __restrict__ idx,
                                                                 const float* __restrict__ weight,
-                                                                float* __restrict__ out, int C,
+                                                                T* __restrict__ out, int C,
                                                                 int M, int N, int c_per_block) {
   const int b = blockIdx.z;
   const int n = blockIdx.x * 256 + threadIdx.x;
@@ -824,8 +853,9 @@ __global__ __launch_bounds__(256) void three_interpolate_kernel(const float* __r
   const int c0 = blockIdx.y * c_per_block;
   const int c1 = min(C, c0 + c_per_block);
   for (int c = c0; c < c1; ++c) {
-    const float* __restrict__ p = points + ((size_t)b * C + c) * M;
-    out[((size_t)b * C + c) * N + n] = __builtin_fmaf(w2, p[i2], __builtin_fmaf(w0, p[i0], w1 * p[i1]));
+    const T* __restrict__ p = points + ((size_t)b * C + c) * M;
+    out[((size_t)b * C + c) * N + n] = pp::narrow<T>(
+        __builtin_fmaf(w2, pp::widen(p[i2]), __builtin_fmaf(w0, pp::widen(p[i0]), w1 * pp::widen(p[i1]))));
   }
 }
 
@@ -1000,10 +1030,10 @@ __global__ __launch_bounds__(256) void three_interpolate_grad_kernel(
 // double): one workgroup per (batch, group of CG channels) keeps CG columns grad_points[b,c,:] in
 // LDS, reads (idx, weight) of a point once for the CG channels and adds the fp32 products
 // grad_out*weight (the reference's rounding, interpolate_gpu.cu:137-139) with ds_add_f64.
-template <int CG>
+template <int CG, typename T = float>  // 16-bit T: widened grad_out, the columns WRITTEN as T(float(sum))
 __global__ __launch_bounds__(1024) void three_interpolate_grad_lds64_kernel(
-    const float* __restrict__ grad_out, const int* __restrict__ idx, const float* __restrict__ weight,
-    float* __restrict__ grad_points, int B, int C, int N, int M) {
+    const T* __restrict__ grad_out, const int* __restrict__ idx, const float* __restrict__ weight,
+    T* __restrict__ grad_points, int B, int C, int N, int M) {
   extern __shared__ __attribute__((aligned(16))) double s_acc64[];  // [CG][M]
   const int groups = (C + CG - 1) / CG;
   const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
@@ -1014,7 +1044,7 @@ __global__ __launch_bounds__(1024) void three_interpolate_grad_lds64_kernel(
   const int t = threadIdx.x;
   for (int k = t; k < CG * M; k += 1024) s_acc64[k] = 0.0;
   __syncthreads();
-  const float* __restrict__ go = grad_out + ((size_t)b * C + c0) * N;
+  const T* __restrict__ go = grad_out + ((size_t)b * C + c0) * N;
   for (int n = t; n < N; n += 1024) {
     const int* id = idx + ((size_t)b * N + n) * 3;
     const float* w = weight + ((size_t)b * N + n) * 3;
@@ -1022,7 +1052,7 @@ __global__ __launch_bounds__(1024) void three_interpolate_grad_lds64_kernel(
     const float w0 = w[0], w1 = w[1], w2 = w[2];
     float g[CG];
 #pragma unroll
-    for (int k = 0; k < CG; ++k) g[k] = go[(size_t)min(k, nc - 1) * N + n];
+    for (int k = 0; k < CG; ++k) g[k] = pp::widen(go[(size_t)min(k, nc - 1) * N + n]);
 #pragma unroll
     for (int k = 0; k < CG; ++k)
       if (k < nc) {
@@ -1034,20 +1064,24 @@ __global__ __launch_bounds__(1024) void three_interpolate_grad_lds64_kernel(
   }
   __syncthreads();
   for (int k = 0; k < nc; ++k) {
-    float* __restrict__ gp = grad_points + ((size_t)b * C + c0 + k) * M;
-    for (int m = t; m < M; m += 1024) gp[m] += (float)s_acc64[(size_t)k * M + m];  // accumulate: the ABI's contract
+    T* __restrict__ gp = grad_points + ((size_t)b * C + c0 + k) * M;
+    if constexpr (std::is_same<T, float>::value) {
+      for (int m = t; m < M; m += 1024) gp[m] += (float)s_acc64[(size_t)k * M + m];  // accumulate: the ABI's contract
+    } else {
+      for (int m = t; m < M; m += 1024) gp[m] = pp::narrow<T>((float)s_acc64[(size_t)k * M + m]);
+    }
   }
 }
 
-template <int CG>
-static int launch_three_interpolate_grad_lds64(const float* grad_out, const int* idx, const float* weight,
-                                               float* grad_points, int B, int C, int N, int M, hipStream_t s) {
+template <int CG, typename T>
+static int launch_three_interpolate_grad_lds64(const T* grad_out, const int* idx, const float* weight,
+                                               T* grad_points, int B, int C, int N, int M, hipStream_t s) {
   static pp::DeviceFlags ok;
-  const hipError_t e = pp::allow_big_lds(three_interpolate_grad_lds64_kernel<CG>, 152 * 1024, ok);
+  const hipError_t e = pp::allow_big_lds(three_interpolate_grad_lds64_kernel<CG, T>, 152 * 1024, ok);
   if (e != hipSuccess) return (int)e;
   const long long wgs = 8LL * ((B + 7) / 8) * ((C + CG - 1) / CG);
   if (wgs > 0x7fffffffLL) return PP_EINVAL;
-  three_interpolate_grad_lds64_kernel<CG><<<dim3((unsigned)wgs), dim3(1024), (size_t)CG * M * sizeof(double), s>>>(
+  three_interpolate_grad_lds64_kernel<CG, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)CG * M * sizeof(double), s>>>(
       grad_out, idx, weight, grad_points, B, C, N, M);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -1116,8 +1150,8 @@ extern "C" int pp_gather_forward_f32(const float* points, const int* idx, float*
   const int cpb = pick_c_per_block(cols, B, C);
   const long long gy = (C + cpb - 1) / cpb;
   if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  gather_fwd_kernel<<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                      (hipStream_t)stream>>>(points, idx, out, C, N, M, cpb);
+  gather_fwd_kernel<float><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
+                             (hipStream_t)stream>>>(points, idx, out, C, N, M, cpb);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }
@@ -1417,8 +1451,8 @@ extern "C" int pp_three_interpolate_f32(const float* points, const int* idx, con
   const int cpb = pick_c_per_block(cols, B, C);
   const long long gy = (C + cpb - 1) / cpb;
   if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  three_interpolate_kernel<<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                             (hipStream_t)stream>>>(points, idx, weight, out, C, M, N, cpb);
+  three_interpolate_kernel<float><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
+                                    (hipStream_t)stream>>>(points, idx, weight, out, C, M, N, cpb);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }
@@ -1581,4 +1615,554 @@ extern "C" int pp_three_interpolate_grad_ordered_f32(const float* grad_out, cons
   if (!ordered_ok(B, 3LL * N, 3, M, 1, workspace, workspace_bytes)) return PP_ENOTSUP;
   return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, workspace,
                      (hipStream_t)stream, true);
+}
+
+// ================================================================================================
+// 16-bit features (DESIGN.md §4 "16-bit features"): gather_points, group_points and three_interpolate on fp16 / bf16
+// FEATURE tensors; indices stay int32, weights fp32.  Copies move 2-byte words (one set of kernels for both types);
+// arithmetic widens to fp32, runs the fp32 kernels' chain and rounds once; the backwards sum in the accumulators of
+// the fp32 forms (group_points_grad_lds64_kernel, three_interpolate_grad_lds64_kernel and ssa_apply_kernel are
+// templates on the element type) and WRITE grad_points.  No 16-bit floating-point atomics anywhere: a backward
+// without an atomic-free form for its shape returns PP_ENOTSUP.
+// The vector forms own EIGHT consecutive elements per lane (16 bytes); every guard names its real requirement, and the
+// 2-byte scalar forms serve any shape: a row (b,c) starts at byte (b*C+c)*N*2, aligned to 16 only if N % 8 == 0.
+// ================================================================================================
+namespace {
+
+typedef uint16_t u16;
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pack2(u16 lo, u16 hi) { return (unsigned)lo | ((unsigned)hi << 16); }
+__device__ __forceinline__ u4v gather8(const u16* s, const pp::i4& a, const pp::i4& b) {
+  return u4v{pack2(s[a.x], s[a.y]), pack2(s[a.z], s[a.w]), pack2(s[b.x], s[b.y]), pack2(s[b.z], s[b.w])};
+}
+
+// gather_points through the LDS (see gather_fwd_lds_kernel): the row is 2 N bytes; VEC: N % 8 == 0, M % 8 == 0 and
+// 16-byte aligned pointers -- 16-byte row loads, two index quads and one 16-byte store per lane
+template <bool VEC>
+__global__ __launch_bounds__(1024) void gather_fwd_lds_b16_kernel(const u16* __restrict__ points,
+                                                                  const int* __restrict__ idx,
+                                                                  u16* __restrict__ out, int B, int C, int N,
+                                                                  int M, int cpb, int groups) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_g16[];
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int b = x + 8 * (y / groups);
+  if (b >= B) return;
+  const int c0 = (y % groups) * cpb;
+  const int c1 = min(C, c0 + cpb);
+  const int t = threadIdx.x;
+  const int* __restrict__ ib = idx + (size_t)b * M;
+  for (int c = c0; c < c1; ++c) {
+    __syncthreads();  // the previous row has been gathered
+    const u16* __restrict__ row = points + ((size_t)b * C + c) * N;
+    u16* __restrict__ o = out + ((size_t)b * C + c) * M;
+    if constexpr (VEC) {
+      for (int e = t; e < (N >> 3); e += 1024) reinterpret_cast<u4v*>(s_g16)[e] = reinterpret_cast<const u4v*>(row)[e];
+      __syncthreads();
+      for (int m = t * 8; m < M; m += 8192) {
+        const pp::i4 ia = *reinterpret_cast<const pp::i4*>(ib + m);
+        const pp::i4 ic = *reinterpret_cast<const pp::i4*>(ib + m + 4);
+        *reinterpret_cast<u4v*>(o + m) = gather8(s_g16, ia, ic);
+      }
+    } else {
+      for (int e = t; e < N; e += 1024) s_g16[e] = row[e];
+      __syncthreads();
+      for (int m = t; m < M; m += 1024) o[m] = s_g16[ib[m]];
+    }
+  }
+}
+
+// group_points, global gathers: VEC8 = a lane owns 8 consecutive (j,k) positions (P % 8 == 0, obs % 8 == 0, idx and
+// out 16-byte aligned; the rows need no alignment: they are read 2 bytes at a time); otherwise one position per lane
+template <bool VEC8>
+__global__ __launch_bounds__(256) void group_points_b16_kernel(const u16* __restrict__ points,
+                                                               const int* __restrict__ idx,
+                                                               u16* __restrict__ out, int C, int N,
+                                                               long long P, int c_per_block, long long obs) {
+  const int b = blockIdx.z;
+  const int c0 = blockIdx.y * c_per_block;
+  const int c1 = min(C, c0 + c_per_block);
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (VEC8) {
+    const long long p = t * 8;
+    if (p >= P) return;
+    const pp::i4 ia = *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p);
+    const pp::i4 ic = *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p + 4);
+    for (int c = c0; c < c1; ++c)
+      *reinterpret_cast<u4v*>(out + (size_t)b * obs + (size_t)c * P + p) =
+          gather8(points + ((size_t)b * C + c) * N, ia, ic);
+  } else {
+    if (t >= P) return;
+    const int i = idx[(size_t)b * P + t];
+    for (int c = c0; c < c1; ++c)
+      out[(size_t)b * obs + (size_t)c * P + t] = points[((size_t)b * C + c) * N + i];
+  }
+}
+
+// group_points, row staged in LDS through registers (see group_points_lds_kernel): a 512-thread workgroup owns
+// 512 * 8 * V consecutive positions of one batch element, keeps their indices in registers for all C channels and
+// streams 16-byte stores; the last chunk may be ragged (P % 8 == 0: an octet exists whole or not at all).
+// Requires the VEC8 conditions, N % 8 == 0 and 16-byte aligned points; 2 N bytes of LDS.
+template <int V>
+__global__ __launch_bounds__(512) void group_points_lds_b16_kernel(const u16* __restrict__ points,
+                                                                   const int* __restrict__ idx,
+                                                                   u16* __restrict__ out, int B, int C, int N,
+                                                                   long long P, int chunks, long long obs) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_r16[];
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int b = x + 8 * (y / chunks);
+  const int chunk = y % chunks;
+  if (b >= B) return;
+  const int t = threadIdx.x;
+  const long long p0 = (long long)chunk * (512 * 8 * V) + t * 8;
+  pp::i4 ia[V], ic[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const long long p = p0 + (long long)v * 4096;
+    ia[v] = p < P ? *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p) : pp::i4{0, 0, 0, 0};
+    ic[v] = p < P ? *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p + 4) : pp::i4{0, 0, 0, 0};
+  }
+  const int n8 = N >> 3;
+  const u4v* __restrict__ rows = reinterpret_cast<const u4v*>(points + (size_t)b * C * N);
+  u16* __restrict__ out_b = out + (size_t)b * obs;
+  for (int c = 0; c < C; ++c) {
+    __syncthreads();  // everyone is done gathering from the previous row
+    for (int e = t; e < n8; e += 512) reinterpret_cast<u4v*>(s_r16)[e] = rows[(size_t)c * n8 + e];
+    __syncthreads();
+    u16* __restrict__ o = out_b + (size_t)c * P;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const long long p = p0 + (long long)v * 4096;
+      const u4v r = gather8(s_r16, ia[v], ic[v]);
+      if (p < P) *reinterpret_cast<u4v*>(o + p) = r;
+    }
+  }
+}
+
+// group_points, rows by LDS-DMA (see group_points_dma1_kernel): one wave instruction moves 1 KiB = 512 elements;
+// whole chunks of 512 * 8 * V positions only; non-temporal 16-byte stores
+template <int V>
+__global__ __launch_bounds__(kDma1Threads) void group_points_dma1_b16_kernel(const u16* __restrict__ points,
+                                                                             const int* __restrict__ idx,
+                                                                             u16* __restrict__ out, int B, int C, int N,
+                                                                             long long P, int chunks, int passes,
+                                                                             int cgroups, int c_per_group,
+                                                                             long long obs) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_d16[];
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int per_b = chunks * cgroups;
+  const int b = x + 8 * (y / per_b);
+  const int rem = y % per_b;
+  const int chunk = rem / cgroups;
+  const int c_begin = (rem % cgroups) * c_per_group;
+  const int c_end = min(C, c_begin + c_per_group);
+  if (b >= B || c_begin >= c_end) return;
+  const int t = threadIdx.x;
+  const int wave = pp::wave_id_uniform();
+  const long long p0 = (long long)chunk * (kDma1Threads * 8 * V) + t * 8;
+  pp::i4 ia[V], ic[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const int* q = idx + (size_t)b * P + p0 + (long long)v * (kDma1Threads * 8);
+    ia[v] = *reinterpret_cast<const pp::i4*>(q);
+    ic[v] = *reinterpret_cast<const pp::i4*>(q + 4);
+  }
+  const int n8 = N >> 3;  // 16-byte units of a row
+  const u4v* __restrict__ row0 = reinterpret_cast<const u4v*>(points + (size_t)b * C * N);
+  u16* __restrict__ out_b = out + (size_t)b * obs;
+  for (int c = c_begin; c < c_end; ++c) {
+    const u4v* __restrict__ row = row0 + (size_t)c * n8;
+    for (int k = 0; k < passes; ++k) {
+      const int e = k * kDma1Threads + t;
+      const int src = e < n8 ? e : n8 - 1;  // surplus lanes re-load the last unit into the buffer's slack
+      u16* dst = s_d16 + (size_t)(k * kDma1Threads + wave * 64) * 8;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(row + src),
+                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    u16* __restrict__ o = out_b + (size_t)c * P;
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+      __builtin_nontemporal_store(gather8(s_d16, ia[v], ic[v]),
+                                  reinterpret_cast<u4v*>(o + p0 + (long long)v * (kDma1Threads * 8)));
+    __builtin_amdgcn_s_barrier();  // every wave has read the row: the next one may land
+    asm volatile("" ::: "memory");
+  }
+}
+
+template <int V>
+bool launch_group_dma1_b16(const u16* points, const int* idx, u16* out, int B, int C, int N, long long P,
+                           long long obs, hipStream_t s) {
+  const long long per_block = (long long)kDma1Threads * 8 * V;
+  if (P % per_block != 0) return false;
+  const long long chunks = P / per_block;
+  const long long base = 8LL * ((B + 7) / 8) * chunks;
+  int cgroups = 1;
+  while (base * cgroups < 512 && cgroups * 2 <= C) cgroups *= 2;
+  const int c_per_group = (C + cgroups - 1) / cgroups;
+  const long long blocks = base * cgroups;
+  const int n8 = N / 8;
+  const int passes = (n8 + kDma1Threads - 1) / kDma1Threads;
+  const size_t lds = (size_t)passes * kDma1Threads * 16;
+  if (lds > 72 * 1024 || chunks > 0x7fffffLL || blocks > 0x7fffffffLL) return false;
+  static pp::DeviceFlags lds_ok;
+  if (pp::allow_big_lds(group_points_dma1_b16_kernel<V>, 80 * 1024, lds_ok) != hipSuccess) return false;
+  group_points_dma1_b16_kernel<V><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
+      points, idx, out, B, C, N, P, (int)chunks, passes, cgroups, c_per_group, obs);
+  return true;
+}
+
+// three_interpolate, channel-group form (see three_interpolate_rows_kernel): CG rows of T staged in LDS (2 M bytes
+// each), widened as they are gathered; the canonical chain in fp32 and one rounding.  VEC: M % 8 == 0, N % 4 == 0,
+// points / idx / weight 16-byte and out 8-byte aligned -- 16-byte staging, four n per lane, one 8-byte store per channel
+template <int CG, bool VEC, typename T>
+__global__ __launch_bounds__(1024) void three_interpolate_rows_b16_kernel(const T* __restrict__ points,
+                                                                          const int* __restrict__ idx,
+                                                                          const float* __restrict__ weight,
+                                                                          T* __restrict__ out, int B, int C,
+                                                                          int M, int N) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_i16[];  // [CG][M] of T
+  T* s_rows = reinterpret_cast<T*>(s_i16);
+  const int groups = (C + CG - 1) / CG;
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int b = x + 8 * (y / groups);
+  if (b >= B) return;
+  const int c0 = (y % groups) * CG;
+  const int nc = min(CG, C - c0);
+  const int t = threadIdx.x;
+  for (int k = 0; k < nc; ++k) {
+    const T* __restrict__ rowp = points + ((size_t)b * C + c0 + k) * M;
+    if constexpr (VEC) {
+      for (int e = t; e < (M >> 3); e += 1024)
+        reinterpret_cast<u4v*>(s_rows + (size_t)k * M)[e] = reinterpret_cast<const u4v*>(rowp)[e];
+    } else {
+      for (int e = t; e < M; e += 1024) s_rows[(size_t)k * M + e] = rowp[e];
+    }
+  }
+  __syncthreads();
+  if constexpr (VEC) {
+    for (int n0 = 4 * t; n0 < N; n0 += 4096) {
+      int ii[12];
+      float ww[12];
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        const pp::i4 q = reinterpret_cast<const pp::i4*>(idx + ((size_t)b * N + n0) * 3)[e];
+        const pp::f4 w = reinterpret_cast<const pp::f4*>(weight + ((size_t)b * N + n0) * 3)[e];
+        ii[4 * e] = q.x; ii[4 * e + 1] = q.y; ii[4 * e + 2] = q.z; ii[4 * e + 3] = q.w;
+        ww[4 * e] = w.x; ww[4 * e + 1] = w.y; ww[4 * e + 2] = w.z; ww[4 * e + 3] = w.w;
+      }
+#pragma unroll
+      for (int k = 0; k < CG; ++k)
+        if (k < nc) {
+          const T* __restrict__ sr = s_rows + (size_t)k * M;
+          T r[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            r[j] = pp::narrow<T>(__builtin_fmaf(ww[3 * j + 2], pp::widen(sr[ii[3 * j + 2]]),
+                                                __builtin_fmaf(ww[3 * j], pp::widen(sr[ii[3 * j]]),
+                                                               ww[3 * j + 1] * pp::widen(sr[ii[3 * j + 1]]))));
+          u2v packed;
+          __builtin_memcpy(&packed, r, 8);
+          *reinterpret_cast<u2v*>(out + ((size_t)b * C + c0 + k) * N + n0) = packed;
+        }
+    }
+  } else {  // no alignment assumed: one n per lane and step, 2-byte stores
+    for (int n = t; n < N; n += 1024) {
+      const int* __restrict__ id = idx + ((size_t)b * N + n) * 3;
+      const float* __restrict__ w = weight + ((size_t)b * N + n) * 3;
+      const int i0 = id[0], i1 = id[1], i2 = id[2];
+      const float w0 = w[0], w1 = w[1], w2 = w[2];
+#pragma unroll
+      for (int k = 0; k < CG; ++k)
+        if (k < nc) {
+          const T* __restrict__ sr = s_rows + (size_t)k * M;
+          out[((size_t)b * C + c0 + k) * N + n] = pp::narrow<T>(
+              __builtin_fmaf(w2, pp::widen(sr[i2]), __builtin_fmaf(w0, pp::widen(sr[i0]), w1 * pp::widen(sr[i1]))));
+        }
+    }
+  }
+}
+
+template <int CG, bool VEC, typename T>
+int launch_three_interpolate_rows_b16(const T* points, const int* idx, const float* weight, T* out, int B, int C,
+                                      int M, int N, hipStream_t s) {
+  static pp::DeviceFlags ok;
+  const hipError_t e = pp::allow_big_lds(three_interpolate_rows_b16_kernel<CG, VEC, T>, 152 * 1024, ok);
+  if (e != hipSuccess) return (int)e;
+  const long long wgs = 8LL * ((B + 7) / 8) * ((C + CG - 1) / CG);
+  if (wgs > 0x7fffffffLL) return PP_EINVAL;
+  three_interpolate_rows_b16_kernel<CG, VEC, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)CG * M * sizeof(T), s>>>(
+      points, idx, weight, out, B, C, M, N);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+template <typename T>
+int three_interpolate_b16(const T* points, const int* idx, const float* weight, T* out, int B, int C, int M, int N,
+                          void* stream) {
+  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
+  if (B == 0 || C == 0 || N == 0) return PP_OK;
+  if (!points || !idx || !weight || !out || M == 0) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int iv = g_interp_variant;
+  const size_t rowb = (size_t)M * sizeof(T);
+  // the channel-group form on the fp32 form's conditions (3: wherever the rows fit -- tests); 2, the fp32 dispatch's
+  // row-at-a-time form, has no 16-bit twin and takes the global form
+  if (iv != 1 && iv != 2 && rowb <= 152 * 1024 &&
+      (iv == 3 || (N >= 2048 && 8LL * ((B + 7) / 8) * ((C + 3) / 4) >= 256))) {
+    const bool vec = M % 8 == 0 && N % 4 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
+                     (uintptr_t)weight % 16 == 0 && (uintptr_t)out % 8 == 0;
+    const bool cg4 = 4 * rowb <= 64 * 1024 && C >= 4;
+    if (vec) {
+      if (cg4) return launch_three_interpolate_rows_b16<4, true, T>(points, idx, weight, out, B, C, M, N, s);
+      return launch_three_interpolate_rows_b16<1, true, T>(points, idx, weight, out, B, C, M, N, s);
+    }
+    if (cg4) return launch_three_interpolate_rows_b16<4, false, T>(points, idx, weight, out, B, C, M, N, s);
+    return launch_three_interpolate_rows_b16<1, false, T>(points, idx, weight, out, B, C, M, N, s);
+  }
+  const long long cols = (N + 255) / 256;
+  const int cpb = pick_c_per_block(cols, B, C);
+  const long long gy = (C + cpb - 1) / cpb;
+  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
+  three_interpolate_kernel<T><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0, s>>>(
+      points, idx, weight, out, C, M, N, cpb);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+int zero_b16(void* p, size_t n, hipStream_t s) { return (int)pp::fill_bytes(p, 0, n * 2, s); }  // +0 in both types
+
+template <typename T>
+int gather_backward_out_b16(const T* grad_out, const int* idx, T* grad_points, int B, int C, int N, int M,
+                            void* ws, size_t ws_bytes, int ordered, void* stream) {
+  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
+  if (B == 0 || C == 0 || N == 0) return PP_OK;
+  if (!grad_points) return PP_EINVAL;
+  if (M == 0) return zero_b16(grad_points, (size_t)B * C * N, (hipStream_t)stream);
+  if (!grad_out || !idx) return PP_EINVAL;
+  if (!ordered_ok(B, M, 1, N, 0, ws, ws_bytes) || (!ordered && g_scatter_mode == 1)) return PP_ENOTSUP;
+  return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, M, 1, N, (long long)C * M, ws, (hipStream_t)stream,
+                     ordered != 0);
+}
+
+template <typename T>
+int group_points_grad_out_b16(const T* grad_out, const int* idx, T* grad_points, int B, int C, int N, int npoint,
+                              int nsample, long long gbs, void* ws, size_t ws_bytes, int ordered, void* stream) {
+  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
+  const long long P = (long long)npoint * nsample;
+  if (B == 0 || C == 0 || N == 0) return PP_OK;
+  if (!grad_points) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (P == 0) return zero_b16(grad_points, (size_t)B * C * N, s);
+  if (!grad_out || !idx || gbs < (long long)C * P) return PP_EINVAL;
+  const bool sorted_ok = ordered_ok(B, P, 1, N, 0, ws, ws_bytes);
+  if (ordered) {
+    if (!sorted_ok) return PP_ENOTSUP;
+    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, gbs, ws, s, true);
+  }
+  const int gv = g_group_grad_variant;
+  constexpr int kW64 = 152 * 1024 / 8;  // destinations per workgroup with a double column
+  const int nsplit = (N + kW64 - 1) / kW64;
+  const long long wgs = 8LL * ((B + 7) / 8) * C * nsplit;
+  const bool columns = gv != 1 && nsplit <= 16 && wgs <= 0x7fffffffLL && (gv == 2 || P >= 4096);
+  const bool sorted = sorted_ok && g_scatter_mode != 1;
+  // the fp32 dispatch's preference: short lists (P <= 4 N) of a problem large enough to pay for the sort go to the
+  // sorted form; otherwise the double column; the sorted form again where no column applies
+  if (sorted && gv != 2 && (!columns || (P <= 4LL * N && (long long)B * P * C >= (1LL << 20))))
+    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, gbs, ws, s, false);
+  if (columns) {
+    const int W = nsplit == 1 ? N : kW64;
+    const bool vec = (uintptr_t)grad_out % 8 == 0 && (uintptr_t)idx % 16 == 0 && P % 4 == 0 && gbs % 4 == 0;
+    static pp::DeviceFlags okv, oks;
+    if (vec) {
+      const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, true, T>, 152 * 1024, okv);
+      if (e != hipSuccess) return (int)e;
+      group_points_grad_lds64_kernel<8, true, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double), s>>>(
+          grad_out, idx, grad_points, B, C, N, P, gbs, nsplit, W, 1);
+    } else {
+      const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, false, T>, 152 * 1024, oks);
+      if (e != hipSuccess) return (int)e;
+      group_points_grad_lds64_kernel<8, false, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double), s>>>(
+          grad_out, idx, grad_points, B, C, N, P, gbs, nsplit, W, 1);
+    }
+    PP_RETURN_IF_LAUNCH_FAILED();
+    return PP_OK;
+  }
+  if (sorted) return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, gbs, ws, s, false);
+  return PP_ENOTSUP;
+}
+
+template <typename T>
+int three_interpolate_grad_out_b16(const T* grad_out, const int* idx, const float* weight, T* grad_points, int B,
+                                   int C, int N, int M, void* ws, size_t ws_bytes, int ordered, void* stream) {
+  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
+  if (B == 0 || C == 0 || M == 0) return PP_OK;
+  if (!grad_points) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) return zero_b16(grad_points, (size_t)B * C * M, s);
+  if (!grad_out || !idx || !weight) return PP_EINVAL;
+  const bool sorted_ok = ordered_ok(B, 3LL * N, 3, M, 1, ws, ws_bytes);
+  if (ordered) {
+    if (!sorted_ok) return PP_ENOTSUP;
+    return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, ws, s, true);
+  }
+  const int gv = g_interp_grad_variant;
+  const size_t col = (size_t)M * sizeof(double);
+  if (gv != 1 && gv != 3 && col <= 152 * 1024 && (gv == 2 || N >= 2048)) {
+    if (C >= 4 && 4 * col <= 152 * 1024)
+      return launch_three_interpolate_grad_lds64<4>(grad_out, idx, weight, grad_points, B, C, N, M, s);
+    if (C >= 2 && 2 * col <= 152 * 1024)
+      return launch_three_interpolate_grad_lds64<2>(grad_out, idx, weight, grad_points, B, C, N, M, s);
+    return launch_three_interpolate_grad_lds64<1>(grad_out, idx, weight, grad_points, B, C, N, M, s);
+  }
+  if (sorted_ok && g_scatter_mode != 1)
+    return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, ws, s, false);
+  return PP_ENOTSUP;
+}
+
+}  // namespace
+
+extern "C" int pp_gather_forward_b16(const void* points_, const int* idx, void* out_, int B, int C, int N, int M,
+                                     void* stream) {
+  const u16* points = (const u16*)points_;
+  u16* out = (u16*)out_;
+  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
+  if (B == 0 || C == 0 || M == 0) return PP_OK;
+  if (!points || !idx || !out || N == 0) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int gv = g_gather_variant;
+  // LDS-staged rows on the fp32 form's conditions (2: wherever the row fits -- tests)
+  if (gv != 1 && (size_t)N * 2 <= 152 * 1024 &&
+      (gv == 2 || ((long long)N <= 16LL * M && (long long)B * C >= 512 && M >= 1024))) {
+    const bool vec = N % 8 == 0 && M % 8 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
+                     (uintptr_t)out % 16 == 0;
+    int cpb = 4;
+    while (cpb > 1 && 8LL * ((B + 7) / 8) * ((C + cpb - 1) / cpb) < 1024) cpb /= 2;
+    const int groups = (C + cpb - 1) / cpb;
+    const long long wgs = 8LL * ((B + 7) / 8) * groups;
+    if (wgs <= 0x7fffffffLL) {
+      static pp::DeviceFlags okv, oks;
+      if (vec) {
+        if (pp::allow_big_lds(gather_fwd_lds_b16_kernel<true>, 152 * 1024, okv) != hipSuccess) return PP_EINVAL;
+        gather_fwd_lds_b16_kernel<true><<<dim3((unsigned)wgs), dim3(1024), (size_t)N * 2, s>>>(points, idx, out, B, C,
+                                                                                               N, M, cpb, groups);
+      } else {
+        if (pp::allow_big_lds(gather_fwd_lds_b16_kernel<false>, 152 * 1024, oks) != hipSuccess) return PP_EINVAL;
+        gather_fwd_lds_b16_kernel<false><<<dim3((unsigned)wgs), dim3(1024), (size_t)N * 2, s>>>(points, idx, out, B, C,
+                                                                                                N, M, cpb, groups);
+      }
+      PP_RETURN_IF_LAUNCH_FAILED();
+      return PP_OK;
+    }
+  }
+  const long long cols = (M + 255) / 256;
+  const int cpb = pick_c_per_block(cols, B, C);
+  const long long gy = (C + cpb - 1) / cpb;
+  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
+  gather_fwd_kernel<u16><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0, s>>>(points, idx, out, C, N,
+                                                                                               M, cpb);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_group_points_strided_b16(const void* points_, const int* idx, void* out_, int B, int C, int N,
+                                           int npoint, int nsample, long long out_batch_stride, void* stream) {
+  const u16* points = (const u16*)points_;
+  u16* out = (u16*)out_;
+  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
+  const long long P = (long long)npoint * nsample;
+  const long long obs = out_batch_stride;
+  if (obs < (long long)C * P) return PP_EINVAL;
+  if (B == 0 || C == 0 || P == 0) return PP_OK;
+  if (!points || !idx || !out || N == 0) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec8 = (P % 8 == 0) && (obs % 8 == 0) && ((uintptr_t)idx % 16 == 0) && ((uintptr_t)out % 16 == 0);
+  const int gv = g_group_variant;
+  // LDS-staged forms, on the fp32 dispatch's conditions: the row (2 N bytes) within 64 KiB, rows 16-byte aligned, enough
+  // channels and positions (a knob value that names an LDS form takes it below that size too: tests)
+  if (gv != 1 && vec8 && N % 8 == 0 && (uintptr_t)points % 16 == 0 && (size_t)N * 2 <= 64 * 1024 && C >= 4 &&
+      (gv != 0 || (long long)B * P >= 256LL * 2048)) {
+    // the LDS-DMA form wherever the positions fill whole chunks of 32768, 16384 or 8192 (the fp32 form's chunks:
+    // 8 / 4 / 2 index octets per thread for its 16 / 8 / 4 quads)
+    bool ok = false;
+    if (gv == 616 || gv == 0) ok = launch_group_dma1_b16<8>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok && (gv == 608 || gv == 0)) ok = launch_group_dma1_b16<4>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok && (gv == 604 || gv == 0)) ok = launch_group_dma1_b16<2>(points, idx, out, B, C, N, P, obs, s);
+    if (ok) {
+      PP_RETURN_IF_LAUNCH_FAILED();
+      return PP_OK;
+    }
+    // ragged chunks, or forced by 2 / 4 / 8 / a value above 100: the register-staged form (one instantiation)
+    constexpr int V = 4;
+    const long long chunks = (P + 512LL * 8 * V - 1) / (512LL * 8 * V);
+    const long long blocks = 8LL * ((B + 7) / 8) * chunks;
+    if (chunks <= 0x7fffffLL && blocks <= 0x7fffffffLL) {
+      group_points_lds_b16_kernel<V><<<dim3((unsigned)blocks), dim3(512), (size_t)N * 2, s>>>(points, idx, out, B, C, N,
+                                                                                            P, (int)chunks, obs);
+      PP_RETURN_IF_LAUNCH_FAILED();
+      return PP_OK;
+    }
+  }
+  const long long threads = vec8 ? P / 8 : P;
+  const long long cols = (threads + 255) / 256;
+  const int cpb = pick_c_per_block(cols, B, C);
+  const long long gy = (C + cpb - 1) / cpb;
+  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
+  const dim3 grid((unsigned)cols, (unsigned)gy, (unsigned)B);
+  if (vec8)
+    group_points_b16_kernel<true><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
+  else
+    group_points_b16_kernel<false><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_three_interpolate_f16(const void* points, const int* idx, const float* weight, void* out, int B,
+                                        int C, int M, int N, void* stream) {
+  return three_interpolate_b16((const pp::f16*)points, idx, weight, (pp::f16*)out, B, C, M, N, stream);
+}
+extern "C" int pp_three_interpolate_bf16(const void* points, const int* idx, const float* weight, void* out, int B,
+                                         int C, int M, int N, void* stream) {
+  return three_interpolate_b16((const pp::bf16*)points, idx, weight, (pp::bf16*)out, B, C, M, N, stream);
+}
+
+extern "C" int pp_gather_backward_out_ws_f16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
+                                             int N, int M, void* workspace, size_t workspace_bytes, int ordered,
+                                             void* stream) {
+  return gather_backward_out_b16((const pp::f16*)grad_out, idx, (pp::f16*)grad_points, B, C, N, M, workspace,
+                                 workspace_bytes, ordered, stream);
+}
+extern "C" int pp_gather_backward_out_ws_bf16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
+                                              int N, int M, void* workspace, size_t workspace_bytes, int ordered,
+                                              void* stream) {
+  return gather_backward_out_b16((const pp::bf16*)grad_out, idx, (pp::bf16*)grad_points, B, C, N, M, workspace,
+                                 workspace_bytes, ordered, stream);
+}
+
+extern "C" int pp_group_points_grad_out_ws_f16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
+                                               int N, int npoint, int nsample, long long grad_out_batch_stride,
+                                               void* workspace, size_t workspace_bytes, int ordered, void* stream) {
+  return group_points_grad_out_b16((const pp::f16*)grad_out, idx, (pp::f16*)grad_points, B, C, N, npoint, nsample,
+                                   grad_out_batch_stride, workspace, workspace_bytes, ordered, stream);
+}
+extern "C" int pp_group_points_grad_out_ws_bf16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
+                                                int N, int npoint, int nsample, long long grad_out_batch_stride,
+                                                void* workspace, size_t workspace_bytes, int ordered, void* stream) {
+  return group_points_grad_out_b16((const pp::bf16*)grad_out, idx, (pp::bf16*)grad_points, B, C, N, npoint, nsample,
+                                   grad_out_batch_stride, workspace, workspace_bytes, ordered, stream);
+}
+
+extern "C" int pp_three_interpolate_grad_out_ws_f16(const void* grad_out, const int* idx, const float* weight,
+                                                    void* grad_points, int B, int C, int N, int M, void* workspace,
+                                                    size_t workspace_bytes, int ordered, void* stream) {
+  return three_interpolate_grad_out_b16((const pp::f16*)grad_out, idx, weight, (pp::f16*)grad_points, B, C, N, M,
+                                        workspace, workspace_bytes, ordered, stream);
+}
+extern "C" int pp_three_interpolate_grad_out_ws_bf16(const void* grad_out, const int* idx, const float* weight,
+                                                     void* grad_points, int B, int C, int N, int M, void* workspace,
+                                                     size_t workspace_bytes, int ordered, void* stream) {
+  return three_interpolate_grad_out_b16((const pp::bf16*)grad_out, idx, weight, (pp::bf16*)grad_points, B, C, N, M,
+                                        workspace, workspace_bytes, ordered, stream);
 }

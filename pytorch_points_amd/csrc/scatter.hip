@@ -18,6 +18,7 @@
 // reference's launch (the CPU oracle) adds them: results are reproducible bit for bit from run to run AND
 // equal to the oracle's.
 #include "pp_common.h"
+#include "pp_b16.h"
 
 namespace {
 
@@ -128,10 +129,12 @@ __global__ __launch_bounds__(kSsaThreads) void ssa_build_kernel(const int* __res
 // One workgroup per (batch, channel).  Per source chunk the values AND the chunk's sorted triples
 // (and weights) are staged in LDS with coalesced loads; a thread then walks its own slice of the
 // triples out of LDS, four at a time (reads first, then the read-modify-writes in order).
-template <bool WEIGHTED>
-__global__ __launch_bounds__(kSsaThreads) void ssa_apply_kernel(const float* __restrict__ src,
+// T = float accumulates into `out` (the fp32 ABI's contract); a 16-bit T is widened as it is staged, summed in the
+// same fp32 slots and WRITTEN, rounded once (DESIGN.md §4 "16-bit features").
+template <bool WEIGHTED, typename T>
+__global__ __launch_bounds__(kSsaThreads) void ssa_apply_kernel(const T* __restrict__ src,
                                                                 const unsigned char* __restrict__ ws,
-                                                                float* __restrict__ out, int B, int C,
+                                                                T* __restrict__ out, int B, int C,
                                                                 long long P, int R, long long Ps, int Nd,
                                                                 int nchunks, int S, long long src_bstride) {
   extern __shared__ __attribute__((aligned(16))) float s_f[];  // s_val[S] | s_ent[S*R] | s_w[S*R]? | s_acc[Nd]
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(kSsaThreads) void ssa_apply_kernel(const float* __r
   const unsigned* __restrict__ entries = reinterpret_cast<const unsigned*>(ws + L.entries) + (size_t)b * P;
   const float* __restrict__ wts = WEIGHTED ? reinterpret_cast<const float*>(ws + L.weights) + (size_t)b * P : nullptr;
   const unsigned* __restrict__ offs = reinterpret_cast<const unsigned*>(ws + L.offsets) + (size_t)b * nchunks * (kSsaThreads + 1);
-  const float* __restrict__ row = src + (size_t)b * src_bstride + (size_t)c * Ps;
+  const T* __restrict__ row = src + (size_t)b * src_bstride + (size_t)c * Ps;
   const int t = threadIdx.x;
   for (int k = t; k < Nd; k += kSsaThreads) s_acc[k] = 0.0f;
   // The next chunk's values / triples / weights travel through registers while the current chunk is
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(kSsaThreads) void ssa_apply_kernel(const float* __r
     for (int u = 0; u < KVMAX; ++u)
       if (u < kv) {
         const long long sidx = s0 + t + (long long)kSsaThreads * u;
-        rv[u] = row[sidx < Ps ? sidx : last];
+        rv[u] = pp::widen(row[sidx < Ps ? sidx : last]);
         if (R == 1) re[u] = entries[sidx < Ps ? sidx : last];
       }
   };
@@ -211,8 +214,12 @@ __global__ __launch_bounds__(kSsaThreads) void ssa_apply_kernel(const float* __r
     }
   }
   __syncthreads();
-  float* __restrict__ o = out + ((size_t)b * C + c) * Nd;
-  for (int k = t; k < Nd; k += kSsaThreads) o[k] += s_acc[k];  // accumulate: the ABI's contract
+  T* __restrict__ o = out + ((size_t)b * C + c) * Nd;
+  if constexpr (std::is_same<T, float>::value) {
+    for (int k = t; k < Nd; k += kSsaThreads) o[k] += s_acc[k];  // accumulate: the ABI's contract
+  } else {
+    for (int k = t; k < Nd; k += kSsaThreads) o[k] = pp::narrow<T>(s_acc[k]);
+  }
 }
 
 }  // namespace
@@ -241,17 +248,18 @@ size_t ssa_workspace_bytes(int B, long long P, int R, int Nd, bool weighted) {
 }
 
 // out[b,c,dst[b,p]] += (weight ? weight[b,p] : 1) * src[b*src_bstride + c*(P/R) + p/R]
-int ssa_run(const float* src, const int* dst, const float* weight, float* out, int B, int C,
-            long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered) {
+template <typename T>
+static int ssa_run_t(const T* src, const int* dst, const float* weight, T* out, int B, int C,
+                     long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered) {
   const long long Ps = P / R;
   const int S = ssa_chunk(R, Nd, weight != nullptr);
   const int nchunks = (int)((Ps + S - 1) / S);
   static pp::DeviceFlags ok_build, ok_a, ok_b;
   hipError_t e = allow_big_lds(ssa_build_kernel, 152 * 1024, ok_build);
   if (e != hipSuccess) return (int)e;
-  e = allow_big_lds(ssa_apply_kernel<false>, 160 * 1024, ok_a);
+  e = allow_big_lds(ssa_apply_kernel<false, T>, 160 * 1024, ok_a);
   if (e != hipSuccess) return (int)e;
-  e = allow_big_lds(ssa_apply_kernel<true>, 160 * 1024, ok_b);
+  e = allow_big_lds(ssa_apply_kernel<true, T>, 160 * 1024, ok_b);
   if (e != hipSuccess) return (int)e;
   unsigned char* ws = (unsigned char*)workspace;
   ssa_build_kernel<<<dim3((unsigned)(B * nchunks)), dim3(kSsaThreads), (size_t)(Nd + Nd / 32 + 1) * sizeof(unsigned), s>>>(
@@ -260,11 +268,25 @@ int ssa_run(const float* src, const int* dst, const float* weight, float* out, i
   const size_t lds = 4 * ((size_t)S + (size_t)S * R * (weight ? 2 : 1) + (size_t)Nd);
   const unsigned blocks = (unsigned)(8 * ((B + 7) / 8) * C);
   if (weight)
-    ssa_apply_kernel<true><<<dim3(blocks), dim3(kSsaThreads), lds, s>>>(src, ws, out, B, C, P, R, Ps, Nd, nchunks, S, src_bstride);
+    ssa_apply_kernel<true, T><<<dim3(blocks), dim3(kSsaThreads), lds, s>>>(src, ws, out, B, C, P, R, Ps, Nd, nchunks, S, src_bstride);
   else
-    ssa_apply_kernel<false><<<dim3(blocks), dim3(kSsaThreads), lds, s>>>(src, ws, out, B, C, P, R, Ps, Nd, nchunks, S, src_bstride);
+    ssa_apply_kernel<false, T><<<dim3(blocks), dim3(kSsaThreads), lds, s>>>(src, ws, out, B, C, P, R, Ps, Nd, nchunks, S, src_bstride);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
+}
+
+int ssa_run(const float* src, const int* dst, const float* weight, float* out, int B, int C,
+            long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered) {
+  return ssa_run_t<float>(src, dst, weight, out, B, C, P, R, Nd, src_bstride, workspace, s, ordered);
+}
+// 16-bit sources: out is WRITTEN (no zero fill in front, no read of it)
+int ssa_run(const f16* src, const int* dst, const float* weight, f16* out, int B, int C,
+            long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered) {
+  return ssa_run_t<f16>(src, dst, weight, out, B, C, P, R, Nd, src_bstride, workspace, s, ordered);
+}
+int ssa_run(const bf16* src, const int* dst, const float* weight, bf16* out, int B, int C,
+            long long P, int R, int Nd, long long src_bstride, void* workspace, hipStream_t s, bool ordered) {
+  return ssa_run_t<bf16>(src, dst, weight, out, B, C, P, R, Nd, src_bstride, workspace, s, ordered);
 }
 
 }  // namespace pp

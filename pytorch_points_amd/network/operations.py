@@ -30,7 +30,9 @@ class GatherFunction(torch.autograd.Function):
         (cols,) = ctx.saved_tensors
         channels, n = ctx.source_shape
         batch, picked = cols.shape
-        grad_features = grad_out.new_zeros((batch, channels, n))      # the kernel accumulates
+        # (the fp32 kernel accumulates; the 16-bit entry points write every element)
+        grad_features = (grad_out.new_zeros if grad_out.dtype is torch.float32 else grad_out.new_empty)(
+            (batch, channels, n))
         sampling.gather_backward(batch, channels, n, picked, grad_out.contiguous(), cols, grad_features)
         return grad_features, None
 
@@ -90,18 +92,23 @@ class _QueryAndGroupFused(torch.autograd.Function):
         npoint = new_xyz.shape[1]
         C = features.shape[1] if features is not None else 0
         cx = 3 if use_xyz else 0
-        out = torch.empty(B, cx + C, npoint, nsample, dtype=torch.float32, device=xyz.device)
+        # 16-bit features: alone they are grouped as they are; beside the fp32 relative coordinates the
+        # output is fp32, torch.cat's promotion in the reference's composition -- the features are widened once
+        fdt = features.dtype if features is not None else torch.float32
+        if use_xyz and fdt in (torch.float16, torch.bfloat16):
+            features = features.float()
+        out = torch.empty(B, cx + C, npoint, nsample, dtype=torch.float32 if use_xyz else fdt, device=xyz.device)
         if use_xyz:
             sampling.group_points_into(xyz.transpose(1, 2).contiguous(), idx, out, 0)
             out[:, :3] -= new_xyz.transpose(1, 2).unsqueeze(-1)
         if features is not None:
             sampling.group_points_into(features.contiguous(), idx, out, cx)
-        ctx.for_backwards = (idx, N, C, cx)
+        ctx.for_backwards = (idx, N, C, cx, fdt)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        idx, N, C, cx = ctx.for_backwards
+        idx, N, C, cx, fdt = ctx.for_backwards
         grad_out = grad_out.contiguous()
         grad_xyz = grad_new_xyz = grad_features = None
         if cx and ctx.needs_input_grad[0]:
@@ -109,7 +116,7 @@ class _QueryAndGroupFused(torch.autograd.Function):
         if cx and ctx.needs_input_grad[1]:
             grad_new_xyz = -grad_out[:, :3].sum(-1).transpose(1, 2).contiguous()
         if C and ctx.needs_input_grad[2]:
-            grad_features = sampling.group_points_grad_from(grad_out, idx, N, cx, C)
+            grad_features = sampling.group_points_grad_from(grad_out, idx, N, cx, C).to(fdt)
         return grad_xyz, grad_new_xyz, grad_features, None, None, None
 
 

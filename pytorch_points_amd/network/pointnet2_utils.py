@@ -48,7 +48,7 @@ class ThreeInterpolate(torch.autograd.Function):
         n = idx.shape[1]
         ctx.save_for_backward(idx, weight)
         ctx.source_points = m
-        out = features.new_empty((batch, channels, n), dtype=torch.float32)
+        out = features.new_empty((batch, channels, n))   # float32, or the features' float16 / bfloat16
         sampling.three_interpolate_wrapper(batch, channels, m, n, features, idx, weight, out)
         return out
 
@@ -57,7 +57,7 @@ class ThreeInterpolate(torch.autograd.Function):
         idx, weight = ctx.saved_tensors
         batch, channels, n = grad_out.shape
         m = ctx.source_points
-        grad_features = grad_out.new_zeros((batch, channels, m), dtype=torch.float32)   # the kernel accumulates
+        grad_features = grad_out.new_zeros((batch, channels, m))   # the fp32 kernel accumulates (16-bit: written)
         sampling.three_interpolate_grad_wrapper(batch, channels, n, m, grad_out.detach().contiguous(), idx, weight,
                                                 grad_features)
         return grad_features, None, None
