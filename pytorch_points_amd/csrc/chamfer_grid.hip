@@ -2387,14 +2387,46 @@ typedef const char __attribute__((address_space(3))) * lds_c_ptr;
 #else
 #define PP_APHASE(n)
 #endif
-// What a tile's front needs from memory, ordered in ONE round trip: lanes 0..47 of `meta` = the reference grid's
-// descriptor (16 words), the query grid's (16), the tile's chunk-table entries (16 words: eight per chunk);
-// `lay` = the reference grid's layer table (lane z: first point of layer z); `qq` = the lane's query.
+// What a tile's front needs from memory, ordered in ONE round trip.  The words that are the same for every lane come
+// through the scalar unit, into SGPRs (the build wrote them, this launch only reads them: the reference grid's
+// descriptor -- words 0..7 `gr`, word 8 `gr8`, words 12..15 `grc` --, of the query grid's the words 8, 10 and 12..15
+// -- `gq8`, `gq10`, `gqc` --, the tile's chunk-table entries `tz`, eight per chunk); a lane loading them for the
+// others cost a v_readlane per word.  Only words that are used are loaded: the register of a word nobody reads is
+// handed to the next scalar result, which then waits for the load -- in front of the query's load.  `lay`, `lay1` =
+// the reference grid's layer table (lane z: first point of layer z and of layer z + 1; the table also holds words
+// this launch writes, and it is indexed by a computed layer: a vector load); `qq` = the lane's query.
+typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// (a uniform address in the constant space: s_load.  The words are dword-aligned, which is all a scalar load asks --
+//  a tile's chunk words start at a multiple of 32 bytes, a descriptor's word 8 at 32 --, so the vector is read through
+//  a type of that alignment, not its natural one.)
+template <typename V>
+__device__ __forceinline__ V uniform_words(const unsigned* p) {
+  typedef V dword_aligned __attribute__((aligned(4)));
+  return *reinterpret_cast<const __attribute__((address_space(4))) dword_aligned*>((uintptr_t)p);
+}
+// (min / max of wave-uniform words on the scalar unit: from min(min(a, b), c) the compiler makes v_min3_i32, with a
+//  v_mov per operand)
+__device__ __forceinline__ int uniform_min(int a, int b) {
+  int r;
+  asm("s_min_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+  return r;
+}
+__device__ __forceinline__ int uniform_max(int a, int b) {
+  int r;
+  asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+  return r;
+}
 struct StageAFront {
   int live;             // the virtual tile exists (the grid is padded to a multiple of eight)
   int b, dir, tile, jj;
   bool valid;
-  unsigned meta, lay;
+  u32x16 tz;
+  u32x8 gr;
+  u32x4 grc, gqc;
+  unsigned gr8, gq8, gq10;
+  unsigned lay, lay1;
   pp::f4 qq;
 };
 __device__ __forceinline__ void stage_a_issue(StageAFront& f, int vb, int per_xcd, int total, int tiles1, int tiles2,
@@ -2413,15 +2445,22 @@ __device__ __forceinline__ void stage_a_issue(StageAFront& f, int vb, int per_xc
   f.jj = f.valid ? f.tile * kTileQ + t : nq - 1;
   const int set = 2 * f.b + f.dir;
   constexpr int kTz = 8 * (kTileQ / pp::kChunk);  // chunk-table words of a tile
-  static_assert(pp::kBuildSlabs == 4 && kTz <= 16, "eight words per chunk, lanes 32..47 of meta");
+  static_assert(pp::kBuildSlabs == 4 && kTz == 16, "eight words per chunk, two chunks per tile: tz");
   const unsigned* __restrict__ gsets = reinterpret_cast<const unsigned*>(ws + L.sets);
   const unsigned* __restrict__ tz = reinterpret_cast<const unsigned*>(ws + L.tile_z) +
                                     ((size_t)(set ^ 1) * L.chunks + (size_t)f.tile * (kTileQ / pp::kChunk)) * 8;
-  const unsigned* __restrict__ src = lane < 16 ? gsets + 16 * (size_t)set + lane
-                                               : (lane < 32 ? gsets + 16 * (size_t)(set ^ 1) + (lane - 16)
-                                                            : tz + min(lane - 32, kTz - 1));
-  f.meta = *src;
-  f.lay = (reinterpret_cast<const unsigned*>(ws + L.layers) + (size_t)set * pp::kLayerWords)[lane < pp::kLayerWords ? lane : 0];
+  const unsigned *gr = gsets + 16 * (size_t)set, *gq = gsets + 16 * (size_t)(set ^ 1);
+  f.gr = uniform_words<u32x8>(gr);
+  f.gr8 = uniform_words<unsigned>(gr + 8);
+  f.grc = uniform_words<u32x4>(gr + 12);
+  f.gq8 = uniform_words<unsigned>(gq + 8);
+  f.gq10 = uniform_words<unsigned>(gq + 10);
+  f.gqc = uniform_words<u32x4>(gq + 12);
+  f.tz = uniform_words<u32x16>(tz);
+  const unsigned* __restrict__ lay = reinterpret_cast<const unsigned*>(ws + L.layers) + (size_t)set * pp::kLayerWords;
+  static_assert(pp::kGridMax + 1 < pp::kLayerWords, "lanes 0 .. gz read layers z and z + 1");
+  f.lay = lay[lane < pp::kLayerWords - 1 ? lane : 0];
+  f.lay1 = lay[lane < pp::kLayerWords - 1 ? lane + 1 : 0];
   const pp::f4* __restrict__ qsorted = reinterpret_cast<const pp::f4*>(ws + L.sorted) + set_point_offset(f.b, f.dir ^ 1, N, M);
   // (an asm load: a plain one the compiler sinks to its first use, a round trip later; it is invisible to the compiler's
   //  counting of loads in flight, so an explicit s_waitcnt vmcnt(0) precedes every use -- grid_stage_a_kernel's top)
@@ -2497,22 +2536,8 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
   PP_QPHASE_DECL;
   StageAFront f;
   stage_a_issue(f, bid, per_xcd, total, tiles1, tiles2, N, M, ws, L, t, lane);
-  // The tile's body is the single pass of a loop, and a settled query's result is stored at the loop's top (never
-  // reached with a result) or behind it: the source shape of the kernel as it was measured.  Written straight-line,
-  // with the store where the result is computed or at the end, the same work compiles to other code (28 fewer
-  // instructions, two fewer registers, another allocation: NOTEBOOK.md, 2026-10-16) that has not been timed; so
-  // does a loop counted from 0.
-  float sv_d = 0.0f;
-  int sv_i = 0, sv_off = 0, sv_dir = 0;
-  bool sv_ok = false;
-  for (int it = bid; it < bid + 1; ++it) {  // (one pass)
   PP_APHASE(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tile's front has landed (the asm load of the query too)
-  if (sv_ok) {
-    (sv_dir ? dist2 : dist1)[sv_off] = sv_d;
-    (sv_dir ? idx2 : idx1)[sv_off] = sv_i;
-  }
-  sv_ok = false;
   if (t == 0) {  // the tile's queue of leftovers and its count of pending queries: ordered before their first use by the
     s_qn = 0u;   // barrier behind the image's arrival -- or by the one a tile whose image does not fit meets instead
     s_tot = 0u;
@@ -2524,41 +2549,32 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
   if (pre_routed != nullptr && f.live && pre_routed[set] != 0u) return;  // (uniform over the direction) served by the every-pair kernel
   const pp::f4 qq = f.qq;
   const unsigned lay = f.lay;
-  auto meta = [&](int l) { return __builtin_amdgcn_readlane((int)f.meta, l); };
   int kmin = 0x7fffffff, kmax = (int)0x80000000;  // the tile's lowest / highest z (pp::zkey)
-  {
-    constexpr int kTz = 8 * (kTileQ / pp::kChunk);
 #pragma unroll
-    for (int w = 0; w < kTz; w += 2) {
-      kmin = min(kmin, meta(32 + w));
-      kmax = max(kmax, meta(32 + w + 1));
-    }
+  for (int w = 0; w < 16; w += 2) {
+    kmin = uniform_min(kmin, (int)f.tz[w]);
+    kmax = uniform_max(kmax, (int)f.tz[w + 1]);
   }
   int* __restrict__ plist = reinterpret_cast<int*>(ws + L.pend) + set_point_offset(b, dir ^ 1, N, M);
   unsigned* __restrict__ pcnt = reinterpret_cast<unsigned*>(ws + L.pend_cnt) + pend_count_offset(b, dir, N, M);
   bool pend = valid;  // (until settled)
   int tried = 0;      // kPendTried once stage A has really been run for the tile
-  GridSet g;          // the reference grid (lanes 0..15 of meta: see the static_assert on GridSet's layout)
+  GridSet g;          // the reference grid (see the static_assert on GridSet's layout)
   static_assert(sizeof(GridSet) == 64 && offsetof(GridSet, gx) == 20 && offsetof(GridSet, useless) == 32 &&
                     offsetof(GridSet, pad) == 36 && offsetof(GridSet, crowd) == 48, "the words read below");
-  g.minx = __int_as_float(meta(0)); g.miny = __int_as_float(meta(1)); g.minz = __int_as_float(meta(2));
-  g.h = __int_as_float(meta(3)); g.invh = __int_as_float(meta(4));
-  g.gx = meta(5); g.gy = meta(6); g.gz = meta(7);
-  // (uniform over the set) grids without crowded cells on both sides (crowd: 1 useless, 2 second-level grids), no
-  // degenerate set, and the query cloud's chunk table exists; no short-circuits: nothing here is worth a branch
-  const bool grids_ok = ((meta(8) | meta(12) | meta(13) | meta(14) | meta(15) | meta(16 + 8) | meta(16 + 12) | meta(16 + 13) |
-                          meta(16 + 14) | meta(16 + 15) | (meta(16 + 10) ^ 1)) == 0);
+  g.minx = __uint_as_float(f.gr[0]); g.miny = __uint_as_float(f.gr[1]); g.minz = __uint_as_float(f.gr[2]);
+  g.h = __uint_as_float(f.gr[3]); g.invh = __uint_as_float(f.gr[4]);
+  g.gx = (int)f.gr[5]; g.gy = (int)f.gr[6]; g.gz = (int)f.gr[7];
+  // (uniform over the set; scalar code) grids without crowded cells on both sides (crowd: 1 useless, 2 second-level
+  // grids), no degenerate set, and the query cloud's chunk table exists
+  const bool grids_ok = ((f.gr8 | f.grc[0] | f.grc[1] | f.grc[2] | f.grc[3] | f.gq8 | f.gqc[0] | f.gqc[1] | f.gqc[2] |
+                          f.gqc[3] | (f.gq10 ^ 1u)) == 0u);
   // ... and the images of this direction's tiles are likely to fit: a tile of kTileQ queries spans about
   // kTileQ gz / nq layers of the reference grid, its image those and three more (one straddled, one either side), each at most as full as
   // the grid's fullest layer.  A volume-filling cloud (coarser grid, fuller layers), a plane (one layer) or a Gaussian
   // (its core) fails this, and its tiles would find their images too large one by one.
   // (the fullest layer counts, not the average: the core of a Gaussian, a face of a box)
-  unsigned lmax;
-  {
-    const unsigned nxt = (unsigned)__shfl_down((int)lay, 1);
-    const float sz = lane < g.gz ? (float)(nxt - lay) : 0.0f;  // (layer populations are < 2^24: exact)
-    lmax = (unsigned)pp::wave_reduce_dpp<false>(sz);
-  }
+  const unsigned lmax = pp::wave_max_u32_dpp1(lane < g.gz ? f.lay1 - lay : 0u);
   const bool fits = (long long)(3 + (kTileQ * g.gz + nq - 1) / nq) * (long long)lmax <= (long long)kTileCap;
   if (f.live && !(grids_ok && fits)) {
     // (uniform over the direction) nothing of this direction is served here: its total is set to "every query" by the
@@ -2637,17 +2653,18 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
       // rows -> byte positions in the image
       const bool wide = x1 > x0;
       const bool va0 = lz >= 0, va1 = lz < gz1, vb0 = ly >= 0, vb1 = ly < gy1;  // the row's layer / line exists
-      const unsigned s0 = r00.x, e0 = (va0 & vb0) ? (wide ? r00.z : r00.y) : s0;
-      const unsigned s1 = r01.x, e1 = (va0 & vb1) ? (wide ? r01.z : r01.y) : s1;
-      const unsigned s2 = r10.x, e2 = (va1 & vb0) ? (wide ? r10.z : r10.y) : s2;
-      const unsigned s3 = r11.x, e3 = (va1 & vb1) ? (wide ? r11.z : r11.y) : s3;
+      // (&& on the lane masks: with & the compiler made 0 / 1 integers of the four flags and masks of those again)
+      const unsigned s0 = r00.x, e0 = (va0 && vb0) ? (wide ? r00.z : r00.y) : s0;
+      const unsigned s1 = r01.x, e1 = (va0 && vb1) ? (wide ? r01.z : r01.y) : s1;
+      const unsigned s2 = r10.x, e2 = (va1 && vb0) ? (wide ? r10.z : r10.y) : s2;
+      const unsigned s3 = r11.x, e3 = (va1 && vb1) ? (wide ? r11.z : r11.y) : s3;
       const unsigned t0 = (e0 - s0 + 3) >> 2, t1 = (e1 - s1 + 3) >> 2, t2 = (e2 - s2 + 3) >> 2, t3 = (e3 - s3 + 3) >> 2;
       const unsigned T1 = t0, T2 = T1 + t1, T3 = T2 + t2, T4 = T3 + t3;
       // group k of the lane's sequence starts at byte a_r + 64 k of the image, r the row k falls in
-      const unsigned a0 = (s0 - tb0) << 4, a1 = ((s1 - tb0) << 4) - (T1 << 6), a2 = ((s2 - tb0) << 4) - (T2 << 6),
-                     a3 = ((s3 - tb0) << 4) - (T3 << 6);
+      const unsigned a0 = (s0 - tb0) << 4, a1 = (s1 - (tb0 + (T1 << 2))) << 4, a2 = (s2 - (tb0 + (T2 << 2))) << 4,
+                     a3 = (s3 - (tb0 + (T3 << 2))) << 4;
       const unsigned endb = ns << 4;  // the padding
-      const int kmax = (int)pp::wave_reduce_dpp<false>((float)T4);
+      const int kmax = (int)pp::wave_max_u32_dpp1(T4);  // the wave's longest sequence
 #ifdef PP_QUERY_PROBE_WALK  // (diagnostic: how full the walk's iterations are -- groups of the lanes against 64 x the wave's longest)
       {
         const float tsum = pp::wave_reduce_dpp<true>((float)T4);
@@ -2691,16 +2708,20 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
         gpos = lt ? pos : gpos;
         best = lt ? gmin : best;
       };
+      // two groups per pass, the next one's fetch ordered in front of each; an odd kmax ends on the group the last
+      // pass fetched, not on a pass of its own (whose second group lay behind every lane's sequence)
       unsigned pcur = pos_of(0), pnext;
       fetch4(pcur, pa);
-      for (int k = 0; k < kmax; k += 2) {
-        pnext = pos_of(k + 1);
+      int kw = 0;
+      for (; kw + 1 < kmax; kw += 2) {
+        pnext = pos_of(kw + 1);
         fetch4(pnext, pb);
         track(pcur, pa);
-        pcur = pos_of(k + 2);
+        pcur = pos_of(kw + 2);
         fetch4(pcur, pa);
         track(pnext, pb);
       }
+      if (kw < kmax) track(pcur, pa);
       if (tie) {  // an exact tie across groups (duplicated points, lattices): the walk again in the exact order
         best = inf;
         auto examine = [&](const pp::f4 (&p)[4]) {
@@ -2714,12 +2735,14 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
           }
         };
         fetch4(pos_of(0), pa);
-        for (int k = 0; k < kmax; k += 2) {
+        int k = 0;
+        for (; k + 1 < kmax; k += 2) {
           fetch4(pos_of(k + 1), pb);
           examine(pa);
           fetch4(pos_of(k + 2), pa);
           examine(pb);
         }
+        if (k < kmax) examine(pa);
       } else {  // the winner is in the group at gpos: lowest index among its minima
         fetch4(gpos, pa);
 #pragma unroll
@@ -2732,13 +2755,11 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
       PP_APHASE(4);
       tried = kPendTried;
       if (valid && best < reach * reach * kBoundSlack) {  // settled (strict; a NaN bound settles nothing)
-        sv_ok = true;  // (stored behind the loop)
-        sv_d = best;
-        sv_i = bidx;
-        sv_off = b * nq + __float_as_int(qq.w);  // (B * (N + M) < 2^31: grid_applicable)
+        const int off = b * nq + __float_as_int(qq.w);  // (B * (N + M) < 2^31: grid_applicable)
+        (dir ? dist2 : dist1)[off] = best;
+        (dir ? idx2 : idx1)[off] = bidx;
         pend = false;
       }
-      sv_dir = dir;
       // ---- what the block left (about one query in 150 on an evenly sampled surface): the cube of Chebyshev radius 1
       // around the query's cell, FROM THE IMAGE (it holds the layers cz - 1 .. cz + 1 of every query of the tile), by
       // a whole wave per query: the tile's leftovers are gathered in a queue in LDS, wave w takes entries w, w + kW,
@@ -2791,7 +2812,7 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
             key = cand < key ? cand : key;  // (a NaN distance -- bits above +inf -- is never taken)
           }
         }
-        key = pp::wave_min_u64_dpp(key);
+        key = pp::wave_min_u64_dpp1(key);
         const float kbest = __uint_as_float((unsigned)(key >> 32));
         const int kidx = (int)(unsigned)key;
         const float wfx = (w.x - g.minx) * g.invh - (float)wcx, wfy = (w.y - g.miny) * g.invh - (float)wcy,
@@ -2832,11 +2853,6 @@ __global__ __launch_bounds__(kTileQ, kTileWaves) void grid_stage_a_kernel(float*
   // count -- 256 adds to one word per direction -- cost the kernel 5 us): lets the list kernel's waves leave at once
   if (t == 0 && s_tot != 0u)
     atomicAdd(reinterpret_cast<unsigned*>(ws + L.layers) + (size_t)set * pp::kLayerWords + pp::kLayerPending, s_tot);
-  }
-  if (sv_ok) {
-    (sv_dir ? dist2 : dist1)[sv_off] = sv_d;
-    (sv_dir ? idx2 : idx1)[sv_off] = sv_i;
-  }
 }
 
 }  // namespace

@@ -209,6 +209,37 @@ __device__ __forceinline__ void wave_reduce6_dpp(float (&v)[6]) {
     asm volatile(PP_DPP6_ROWS("v_max_f32_dpp") "s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
 }
 
+// One wave-wide max in the same fused form (`op v, v, v <dpp>` in place: six VALU instructions, where update_dpp +
+// op compiles to a v_mov, a DPP v_mov and one or two more per step), for a single unsigned word (max or min);
+// the result comes back as a wave-uniform value.  One chain has nothing to interleave with, so the two
+// wait states between a VALU write of a VGPR and its DPP read are an s_nop 1 in front of every step.  Every lane
+// must be active.
+#define PP_DPP1_WAVE(OP)                                                                             \
+  "s_nop 1\n\t" OP " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"                          \
+  "s_nop 1\n\t" OP " %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"                          \
+  "s_nop 1\n\t" OP " %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"                          \
+  "s_nop 1\n\t" OP " %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"                          \
+  "s_nop 1\n\t" OP " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                       \
+  "s_nop 1\n\t" OP " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                       \
+  "s_nop 1"
+__device__ __forceinline__ unsigned wave_max_u32_dpp1(unsigned v) {
+  asm volatile(PP_DPP1_WAVE("v_max_u32_dpp") : "+v"(v));
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ unsigned wave_min_u32_dpp1(unsigned v) {
+  asm volatile(PP_DPP1_WAVE("v_min_u32_dpp") : "+v"(v));
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+// ... of 64-bit keys.  (wave_min_u32_dpp / wave_min_u64_dpp below give the same results through update_dpp + compare +
+// select, three times the instructions; they stay for the list kernel's wave cubes, whose code is not touched here.
+// New callers want the fused forms.)
+__device__ __forceinline__ unsigned long long wave_min_u64_dpp1(unsigned long long key) {
+  const unsigned hi = (unsigned)(key >> 32), lo = (unsigned)key;
+  const unsigned mh = wave_min_u32_dpp1(hi);
+  const unsigned ml = wave_min_u32_dpp1(hi == mh ? lo : 0xffffffffu);
+  return ((unsigned long long)mh << 32) | ml;
+}
+
 // Wave-wide minimum of an unsigned word through DPP (VALU-rate; __shfl_xor is six dependent ds_bpermute round trips):
 // the result as a wave-uniform value.  Every lane must be active.
 __device__ __forceinline__ unsigned wave_min_u32_dpp(unsigned v) {
