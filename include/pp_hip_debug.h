@@ -18,9 +18,8 @@ extern "C" {
 /* Chamfer forward: 0 automatic, 1 brute force (every pair), 2 grid search wherever structurally possible */
 void pp_debug_set_nmdistance_search(int mode);
 /* brute-force kernel form (chamfer.hip).  C == 3: 0 automatic, which takes one of 1 = <Q 1 query per lane, G 8 points
- * per group>, 1002 = <2, 8, packed fp32>, 1416 = <4, 16, packed>; 416 = <4, 16>, 1008 = <8, 8, packed>, 2004 = <4, 8,
- * packed, prefetch>, 3004 = <4, 8, prefetch> are forced by the range tests only; any other value makes the forward
- * return PP_EINVAL.  C != 3: 9 = the one-lane-per-query kernels, any other value automatic */
+ * per group>, 1002 = <2, 8, packed fp32>, 1416 = <4, 16, packed>; any other value makes the forward return PP_EINVAL.
+ * C != 3: 9 = the one-lane-per-query kernels, any other value automatic */
 void pp_debug_set_nmdistance_variant(int variant);
 /* grid search, unlabeled: 0 = the stage-A kernel, then the list kernel over what it left (default; any other value
  * means this too); -1 = no stage-A kernel, the whole-search kernel serves every query */
@@ -38,8 +37,8 @@ void pp_debug_set_nmdistance_row_bitmap(int off);
 /* labeled Chamfer brute force: 1 = the one-lane-per-query kernel */
 void pp_debug_set_labeled_variant(int variant);
 /* Chamfer backward: 0 automatic (double LDS accumulators for C == 3 from N + M = 4096), 1 global atomics, 2 LDS fp32
- * columns, 4 = 0; 3 and any other value: no double accumulators, i.e. the CSR lists where they apply.  (The
- * deterministic form is an entry point of its own, pp_nmdistance_backward_ordered_f32.) */
+ * columns; any other value means 0.  (The deterministic form, the ordered CSR lists, is an entry point of its own,
+ * pp_nmdistance_backward_ordered_f32.) */
 void pp_debug_set_nmdistance_backward_variant(int variant);
 /* per-kernel HIP-event timing of the grid forward, read back after the call: the build and the search's two launches
  * (stage A by tiles, then what it left); stage_a_ms = 0 without a stage-A kernel */

@@ -42,12 +42,12 @@ constexpr int kBlock = 64 * kWavesPerBlock;
 // is a candidate only if its label equals the query's (compared as floats, :89) -- its distance
 // is replaced by +inf otherwise (one v_cmp_eq + one v_cndmask per pair); a query whose minimum is
 // still +inf has no candidate: idx -1, dist 0 (:110-113).
-template <int Q, int G, bool PK, bool PF, bool LAB>
+template <int Q, int G, bool PK, bool LAB>
 __device__ __forceinline__ void nmdist_tile(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, float* __restrict__ dist1,
     int* __restrict__ idx1, float* __restrict__ dist2, int* __restrict__ idx2, int N, int M, const int b,
     const bool second, const int tile, const float* __restrict__ label1, const float* __restrict__ label2) {
-  static_assert(!(LAB && PF), "labels are not combined with the prefetch form");
+  static_assert(!LAB || PK, "the labeled kernel is a packed form");
   static_assert(G % 2 == 0, "groups are consumed two reference points per v_min3");
   constexpr int TQ = 64 * Q;  // queries per workgroup
   __shared__ float s_best[kWavesPerBlock][TQ];
@@ -124,10 +124,6 @@ __device__ __forceinline__ void nmdist_tile(
         for (int i = 0; i < Q; ++i) {
           float da = chamfer_d3(rr[3 * p + 0], rr[3 * p + 1], rr[3 * p + 2], qx[i], qy[i], qz[i]);
           float db = chamfer_d3(rr[3 * p + 3], rr[3 * p + 4], rr[3 * p + 5], qx[i], qy[i], qz[i]);
-          if constexpr (LAB) {
-            da = lq[i] == rl[p] ? da : __builtin_inff();
-            db = lq[i] == rl[p + 1] ? db : __builtin_inff();
-          }
           nb[i] = pp::min3(da, db, nb[i]);
         }
       }
@@ -138,30 +134,10 @@ __device__ __forceinline__ void nmdist_tile(
       best[i] = nb[i];
     }
   };
-  if constexpr (PF) {
-    // ping-pong SGPR sets: the scalar loads of group g+1 are in flight while group g is scanned.
-    // Scalar loads return out of order (only lgkmcnt(0) exists), so each set is "used" before the
-    // next loads are issued -- otherwise waiting for it would also wait for them.
-    if (g0 < g1) {
-      float ra[G * 3], rb[G * 3];
-      load_group(ra, g0);
-      int g = g0;
-      for (; g + 1 < g1; g += 2) {
-        load_group(rb, g + 1);
-        scan_group(ra, g);
-        asm volatile("" ::"s"(rb[0]), "s"(rb[G * 3 - 1]));
-        load_group(ra, g + 2 < g1 ? g + 2 : g1 - 1);
-        scan_group(rb, g + 1);
-        asm volatile("" ::"s"(ra[0]), "s"(ra[G * 3 - 1]));
-      }
-      if (g < g1) scan_group(ra, g);
-    }
-  } else {
-    for (int g = g0; g < g1; ++g) {
-      float rr[G * 3];
-      load_group(rr, g);
-      scan_group(rr, g);
-    }
+  for (int g = g0; g < g1; ++g) {
+    float rr[G * 3];
+    load_group(rr, g);
+    scan_group(rr, g);
   }
 
   // ---- recover the index inside the recorded group ------------------------------------------
@@ -231,7 +207,7 @@ __device__ __forceinline__ void nmdist_tile(
   }
 }
 
-template <int Q, int G, bool PK, bool PF, bool LAB = false>
+template <int Q, int G, bool PK, bool LAB = false>
 __global__ __launch_bounds__(kBlock) void nmdist_fwd_c3_kernel(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, float* __restrict__ dist1,
     int* __restrict__ idx1, float* __restrict__ dist2, int* __restrict__ idx2, int N, int M,
@@ -243,8 +219,8 @@ __global__ __launch_bounds__(kBlock) void nmdist_fwd_c3_kernel(
   const int b = V / per_b;
   const int r = V - b * per_b;
   const bool second = r >= tiles1;
-  nmdist_tile<Q, G, PK, PF, LAB>(xyz1, xyz2, dist1, idx1, dist2, idx2, N, M, b, second,
-                                 second ? r - tiles1 : r, label1, label2);
+  nmdist_tile<Q, G, PK, LAB>(xyz1, xyz2, dist1, idx1, dist2, idx2, N, M, b, second,
+                             second ? r - tiles1 : r, label1, label2);
 }
 
 // The same tile for the directions the grid search has routed here (chamfer_grid.hip, round 6: a direction whose
@@ -263,8 +239,8 @@ __global__ __launch_bounds__(kBlock) void nmdist_fwd_c3_routed_kernel(
   const int r = V - b * per_b;
   const bool second = r >= tiles1;
   if (routed[(size_t)(2 * b + (second ? 1 : 0)) * stride] == 0u) return;
-  nmdist_tile<Q, G, PK, false, false>(xyz1, xyz2, dist1, idx1, dist2, idx2, N, M, b, second,
-                                      second ? r - tiles1 : r, nullptr, nullptr);
+  nmdist_tile<Q, G, PK, false>(xyz1, xyz2, dist1, idx1, dist2, idx2, N, M, b, second,
+                               second ? r - tiles1 : r, nullptr, nullptr);
 }
 
 // Generic point dimension (C != 3): one lane per query, reference point wave-uniform, plain
@@ -460,13 +436,12 @@ __global__ __launch_bounds__(1024) void nmdist_bwd_lds_kernel(
 // scans the counts, fills the lists (integer atomics again), and then one lane per k sums its own
 // term and its list in registers and writes the 12-byte gradient row once.
 constexpr int kCsrSlices = 4;  // workgroups per (batch, target cloud)
-// ORDERED (deterministic mode, pp_nmdistance_backward_ordered_f32): every list is sorted by source index and
+// This is the deterministic mode (pp_nmdistance_backward_ordered_f32): every list is sorted by source index and
 // the terms are added in the order of a sequential loop over the reference's two launches -- first launch
 // (cloud 1 -> cloud 2): own terms into gradxyz1, scattered terms into gradxyz2 in ascending source order;
 // second launch mirrored -- i.e. gradxyz1[j] = (0 + own) - s(i1) - s(i2) ... and gradxyz2[k] = ((0 - s(j1)) -
 // s(j2) ...) + own.  No floating-point atomics anywhere, so the result is reproducible bit for bit, and it
 // equals the CPU oracle's (the restatement under oracle/: oracle_chamfer_backward) bit for bit.
-template <bool ORDERED>
 __global__ __launch_bounds__(1024) void nmdist_bwd_csr_kernel(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, const float* __restrict__ gd1,
     const float* __restrict__ gd2, const int* __restrict__ idx1, const int* __restrict__ idx2,
@@ -563,21 +538,18 @@ __global__ __launch_bounds__(1024) void nmdist_bwd_csr_kernel(
       oz_ = g * (tz - xo[3 * (size_t)j2 + 2]);
     }
     const unsigned e0 = s_start[kk], e1 = s_start[kk + 1];
-    if (ORDERED) {  // ascending source index (the cursors filled the list in arrival order)
-      unsigned* lst = s_list + e0;
-      pp::lane_sort(
-          e1 - e0, [&](unsigned i) { return lst[i]; },
-          [&](unsigned i, unsigned j) {
-            const unsigned v = lst[i];
-            lst[i] = lst[j];
-            lst[j] = v;
-          });
-    }
+    unsigned* lst = s_list + e0;  // ascending source index (the cursors filled the list in arrival order)
+    pp::lane_sort(
+        e1 - e0, [&](unsigned i) { return lst[i]; },
+        [&](unsigned i, unsigned j) {
+          const unsigned v = lst[i];
+          lst[i] = lst[j];
+          lst[j] = v;
+        });
     // cloud 1's rows receive their own term first (first launch), cloud 2's last (second launch); a row
     // without an own term (labeled Chamfer, idx < 0) receives none at all, as in the reference (:175)
-    const bool own_first = !ORDERED || !second;
     float ax = 0.0f, ay = 0.0f, az = 0.0f;
-    if (own_first && j2 >= 0) {
+    if (!second && j2 >= 0) {
       ax += ox_; ay += oy_; az += oz_;
     }
     for (unsigned e = e0; e < e1; ++e) {  // scattered terms (:181)
@@ -587,7 +559,7 @@ __global__ __launch_bounds__(1024) void nmdist_bwd_csr_kernel(
       ay += -(g * (xo[3 * (size_t)j + 1] - ty));
       az += -(g * (xo[3 * (size_t)j + 2] - tz));
     }
-    if (!own_first && j2 >= 0) {
+    if (second && j2 >= 0) {
       ax += ox_; ay += oy_; az += oz_;
     }
     out[3 * (size_t)k] = ax;
@@ -789,7 +761,7 @@ __global__ void fill_zero_kernel(float* __restrict__ a, int* __restrict__ b, lon
   }
 }
 
-template <int Q, int G, bool PK = false, bool PF = false>
+template <int Q, int G, bool PK = false>
 int launch_fwd_c3(const float* xyz1, const float* xyz2, float* dist1, int* idx1, float* dist2,
                   int* idx2, int B, int N, int M, hipStream_t s) {
   constexpr int TQ = 64 * Q;
@@ -797,7 +769,7 @@ int launch_fwd_c3(const float* xyz1, const float* xyz2, float* dist1, int* idx1,
   const long long total = (long long)B * (tiles1 + tiles2);
   if (total > 0x7fffff00LL) return PP_EINVAL;
   const int per_xcd = (int)((total + 7) / 8);
-  nmdist_fwd_c3_kernel<Q, G, PK, PF><<<dim3(per_xcd * 8), dim3(kBlock), 0, s>>>(
+  nmdist_fwd_c3_kernel<Q, G, PK><<<dim3(per_xcd * 8), dim3(kBlock), 0, s>>>(
       xyz1, xyz2, dist1, idx1, dist2, idx2, N, M, tiles1, tiles2, (int)total, per_xcd);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
@@ -978,9 +950,8 @@ int zero_outputs(float* dist1, int* idx1, float* dist2, int* idx2, int B, int N,
 }  // namespace
 
 // Tuning override for benchmarking the forms in one process (bench.py --variant).  C == 3: 0 = automatic, which takes
-// 1 = <Q 1, G 8>, 1002 = <2, 8, packed> or 1416 = <4, 16, packed>; 416 = <4, 16>, 1008 = <8, 8, packed>, 2004 =
-// <4, 8, packed, prefetch>, 3004 = <4, 8, prefetch> are kept for tests/test_gpu_range.py, which forces them over the
-// fp32 range; any other value is PP_EINVAL.  C != 3: 9 = the one-lane-per-query kernels, every other value automatic.
+// 1 = <Q 1, G 8>, 1002 = <2, 8, packed> or 1416 = <4, 16, packed>; any other value is PP_EINVAL.  C != 3: 9 = the
+// one-lane-per-query kernels, every other value automatic.
 static pp::Knob g_fwd_variant;
 extern "C" void pp_debug_set_nmdistance_variant(int v) { g_fwd_variant.set(v); }
 
@@ -1017,12 +988,8 @@ extern "C" int pp_nmdistance_forward_f32(const float* xyz1, const float* xyz2, f
     if (variant == 0) variant = q >= 4LL * 256 * 1024 ? 1416 : (q >= 2LL * 256 * 512 ? 1002 : 1);
     switch (variant) {
       case 1: return launch_fwd_c3<1, 8>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 416: return launch_fwd_c3<4, 16>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 1002: return launch_fwd_c3<2, 8, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 1008: return launch_fwd_c3<8, 8, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       case 1416: return launch_fwd_c3<4, 16, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 2004: return launch_fwd_c3<4, 8, true, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
-      case 3004: return launch_fwd_c3<4, 8, false, true>(xyz1, xyz2, dist1, idx1, dist2, idx2, B, N, M, s);
       default: return PP_EINVAL;
     }
   }
@@ -1082,7 +1049,7 @@ extern "C" int pp_labeled_nmdistance_forward_f32(const float* xyz1, const float*
     const long long tot = (long long)B * (t1 + t2);
     if (tot > 0x7fffff00LL) return PP_EINVAL;
     const int per_xcd = (int)((tot + 7) / 8);
-    nmdist_fwd_c3_kernel<Q, G, true, false, true><<<dim3(per_xcd * 8), dim3(kBlock), 0, s>>>(
+    nmdist_fwd_c3_kernel<Q, G, true, true><<<dim3(per_xcd * 8), dim3(kBlock), 0, s>>>(
         xyz1, xyz2, dist1, idx1, dist2, idx2, N, M, t1, t2, (int)tot, per_xcd, label1, label2);
     PP_RETURN_IF_LAUNCH_FAILED();
     return PP_OK;
@@ -1097,8 +1064,7 @@ extern "C" int pp_labeled_nmdistance_forward_f32(const float* xyz1, const float*
 }
 
 // 0 = automatic (double LDS accumulators for C == 3, N + M >= 4096); 1 = force the global-atomic form; 2 = force
-// the fp32 LDS-column form; 4 = same as 0; 3 and every other value = skip the double accumulators, i.e. the CSR
-// form where it applies   (tests and tuning)
+// the fp32 LDS-column form; every other value means 0   (tests and tuning)
 static pp::Knob g_bwd_variant;
 extern "C" void pp_debug_set_nmdistance_backward_variant(int v) { g_bwd_variant.set(v); }
 
@@ -1121,7 +1087,7 @@ extern "C" int pp_nmdistance_backward_f32(const float* xyz1, const float* xyz2,
   if (!xyz1 || !xyz2 || !graddist1 || !graddist2 || !idx1 || !idx2 || !gradxyz1 || !gradxyz2)
     return PP_EINVAL;
   // double LDS accumulators: C == 3; slices of at most 4096 points (96 KiB + 48 KiB of coordinates), at least 4 per cloud
-  if ((g_bwd_variant == 0 || g_bwd_variant == 4) && C == 3 && N + M >= 4096) {
+  if (g_bwd_variant != 1 && g_bwd_variant != 2 && C == 3 && N + M >= 4096) {
     const int big = N > M ? N : M;
     int slices = (big + 4095) / 4096;
     if (slices < 4) slices = 4;  // 4 measured best at config 2 (8: 38 us, 16: 40 us)
@@ -1139,22 +1105,6 @@ extern "C" int pp_nmdistance_backward_f32(const float* xyz1, const float* xyz2,
       const int total = B * 2 * slices, per_xcd = (total + 7) / 8;
       (vec ? nmdist_bwd_lds64_kernel<true> : nmdist_bwd_lds64_kernel<false>)<<<dim3((unsigned)(per_xcd * 8)), dim3(1024), (size_t)slice_len * 36, s>>>(
           xyz1, xyz2, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2, N, M, slice_len, slices, total, per_xcd);
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
-    }
-  }
-  // CSR form (no fp atomics): C == 3, slice bookkeeping + the other cloud's list fit the LDS
-  if (g_bwd_variant != 1 && g_bwd_variant != 2 && C == 3 && N + M >= 4096) {
-    const int big = N > M ? N : M;
-    const int slice_len = (big + kCsrSlices - 1) / kCsrSlices;
-    const size_t lds = ((size_t)2 * slice_len + 1 + big) * sizeof(unsigned);
-    if (lds <= 150 * 1024 && (long long)B * 2 * kCsrSlices <= 0x7fffffffLL) {
-      static pp::DeviceFlags lds_ok;
-      // (the kernel also has 64 bytes of static LDS: the dynamic limit must leave room for them)
-      const hipError_t e = pp::allow_big_lds(nmdist_bwd_csr_kernel<false>, 152 * 1024, lds_ok);
-      if (e != hipSuccess) return (int)e;
-      nmdist_bwd_csr_kernel<false><<<dim3((unsigned)(B * 2 * kCsrSlices)), dim3(1024), lds, s>>>(
-          xyz1, xyz2, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2, N, M, slice_len);
       PP_RETURN_IF_LAUNCH_FAILED();
       return PP_OK;
     }
@@ -1183,7 +1133,7 @@ extern "C" int pp_nmdistance_backward_f32(const float* xyz1, const float* xyz2,
   return PP_OK;
 }
 
-// Deterministic mode: the CSR form with ordered lists (see nmdist_bwd_csr_kernel<true>).  C == 3 and clouds whose
+// Deterministic mode: the CSR form with ordered lists (see nmdist_bwd_csr_kernel).  C == 3 and clouds whose
 // bookkeeping fits the LDS (max(N, M) up to ~19000 points); PP_ENOTSUP otherwise -- there is no deterministic
 // substitute for other shapes.
 extern "C" int pp_nmdistance_backward_ordered_f32(const float* xyz1, const float* xyz2, const float* graddist1,
@@ -1201,9 +1151,10 @@ extern "C" int pp_nmdistance_backward_ordered_f32(const float* xyz1, const float
   const size_t lds = ((size_t)2 * slice_len + 1 + big) * sizeof(unsigned);
   if (lds > 150 * 1024 || (long long)B * 2 * kCsrSlices > 0x7fffffffLL) return PP_ENOTSUP;
   static pp::DeviceFlags lds_ok;
-  const hipError_t e = pp::allow_big_lds(nmdist_bwd_csr_kernel<true>, 152 * 1024, lds_ok);
+  // (the kernel also has 64 bytes of static LDS: the dynamic limit must leave room for them)
+  const hipError_t e = pp::allow_big_lds(nmdist_bwd_csr_kernel, 152 * 1024, lds_ok);
   if (e != hipSuccess) return (int)e;
-  nmdist_bwd_csr_kernel<true><<<dim3((unsigned)(B * 2 * kCsrSlices)), dim3(1024), lds, (hipStream_t)stream>>>(
+  nmdist_bwd_csr_kernel<<<dim3((unsigned)(B * 2 * kCsrSlices)), dim3(1024), lds, (hipStream_t)stream>>>(
       xyz1, xyz2, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2, N, M, slice_len);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;

@@ -129,6 +129,30 @@ def test_workspace_size_queries_are_host_only():
     assert L.pp_furthest_sampling_f32(None, None, None, 2, 8, 4, 99, None, 0, None) != 0  # null / bad seed
 
 
+def bq_grid_lds(n, ns):
+    """ball_grid.hip's bq_query_lds(N, nsample, 16) restated (also serves tests/test_gpu_sampling.py): the point bitmap
+    in whole quads of words, 448 staged candidates of 16 bytes, 16 rows of nsample + 1 indices of 2 bytes (N <= 65536;
+    4 above)"""
+    return (-(-n // 32) + 3) // 4 * 16 + 448 * 16 + 16 * (ns + 1) * (2 if n <= 65536 else 4)
+
+
+def bq_grid_largest_nsample(n):
+    """the largest nsample whose rows fit the 128 KiB that pp_ball_query_workspace_bytes admits"""
+    return max(k for k in range(1, 8192) if bq_grid_lds(n, k) <= 128 * 1024)
+
+
+@pytest.mark.parametrize("n", [4096, 65536])
+def test_ball_query_workspace_is_offered_exactly_where_the_grid_kernels_rows_fit(n):
+    """pp_ball_query_workspace_bytes offers the grid path only where the query kernel's dynamic LDS at its default
+    of 16 centres a wave (four lanes each) fits 128 KiB, so with a workspace that it has sized the launch never has
+    to take fewer rows per wave."""
+    ns = bq_grid_largest_nsample(n)
+    assert ns == {4096: 3855, 65536: 3615}[n]   # (4096: exactly 128 KiB; 3854 is the last size strictly below)
+    L = _lib.lib()
+    assert L.pp_ball_query_workspace_bytes(1, n, 64, ns) > 0
+    assert L.pp_ball_query_workspace_bytes(1, n, 64, ns + 1) == 0
+
+
 def test_no_cpu_fallback():
     from pytorch_points_amd.network.model_loss import nndistance, labeled_nndistance
     from pytorch_points_amd.network.operations import gather_points, ball_query, grouping_operation

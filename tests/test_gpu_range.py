@@ -93,7 +93,7 @@ def _pair(fam, var, n, seed):
 CHAMFER_PATHS = [{}, {"nmdistance_search": 1}, {"nmdistance_search": 2},
                  {"nmdistance_search": 2, "nmdistance_routing": 1}, {"nmdistance_search": 2, "nmdistance_routing": 2},
                  {"nmdistance_search": 2, "nmdistance_build": 1}, {"nmdistance_search": 2, "nmdistance_tile": -1}] + \
-                [{"nmdistance_search": 1, "nmdistance_variant": v} for v in (1, 416, 1008, 2004, 3004)]
+                [{"nmdistance_search": 1, "nmdistance_variant": v} for v in (1, 1002, 1416)]
 
 
 def _nnd(cuda, x1, x2):
@@ -167,7 +167,7 @@ def test_chamfer_backward(cuda, fam, var):
     finally:
         torch.use_deterministic_algorithms(before)
     assert _eq(r1, o1) and _eq(r2, o2), "%s: the ordered backward differs from the oracle: %s" % (fam, _first(r1, o1))
-    for v in (1, 2, 3, 4):
+    for v in (0, 1, 2):
         with knobs(nmdistance_backward_variant=v):
             r1, r2 = run()
         _bounded(r1, ex[0], ab[0], cnt[0], what="%s gradxyz1 variant %d" % (fam, v))

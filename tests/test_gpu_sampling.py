@@ -434,6 +434,34 @@ def test_ball_query_edges(cuda, bq_path, b, n, m, r, ns):
     assert np.array_equal(idx.cpu().numpy(), oracle.ball_query(c, x, r, ns))
 
 
+@pytest.mark.parametrize("search", [0, 2])
+def test_ball_query_grid_largest_rows(cuda, search):
+    """The grid kernel at the largest dynamic LDS it can be launched with -- pp_ball_query_workspace_bytes admits a
+    shape only if its rows fit 128 KiB, which at N = 4096 is nsample <= 3855 (exactly 128 KiB there; 3854 is the last
+    size below it) -- and the first nsample beyond, which the scan kernels serve."""
+    import ctypes
+    from pytorch_points_amd import _lib
+    from pytorch_points_amd._ext import sampling
+    from test_abi_and_host import bq_grid_largest_nsample
+    n, m, r = 4096, 64, 0.2
+    fits = bq_grid_largest_nsample(n)
+    assert fits == 3855
+    x = S.unit_sphere(41, 1, n)
+    fidx, _ = oracle.furthest_sampling(x, m, 0)
+    c = np.take_along_axis(x, fidx[..., None].astype(np.int64), 1)
+    knob = _lib.lib().pp_debug_set_ball_query_search
+    knob.argtypes = [ctypes.c_int]
+    knob.restype = None
+    knob(search)
+    try:
+        for ns in (fits - 1, fits, fits + 1):
+            assert (_lib.lib().pp_ball_query_workspace_bytes(1, n, m, ns) > 0) == (ns <= fits)
+            idx = sampling.ball_query(_t(c, cuda), _t(x, cuda), r, ns)
+            assert np.array_equal(idx.cpu().numpy(), oracle.ball_query(c, x, r, ns)), "nsample %d" % ns
+    finally:
+        knob(0)
+
+
 # --------------------------------------------------------------------------------- group points
 @pytest.fixture(params=["auto", "global_atomics", "lds_columns"])
 def group_grad_path(request, cuda):
