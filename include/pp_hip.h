@@ -446,6 +446,32 @@ int pp_knn_laplacian_forward_f32(const float* points, const long long* idx, floa
 int pp_knn_laplacian_backward_f32(const long long* idx, const float* grad_lap, float* grad_points, int B, int N, int K,
                                   int D, int ordered, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- edge features ---------------------------------------------------------------------------
+ * The edge tensor of an EdgeConv layer (network/layers.py:41-62,88-109); contract in DESIGN.md "Edge features".
+ * x (B,C,N), query (B,C,P), out (B,2C,P,K) of one element type: dtype 0 = fp32, 1 = fp16, 2 = bf16; idx (B,P,K) int64
+ * (idx64 != 0) or int32.
+ * pp_edge_features_forward: out[b,c,p,k] = query[b,c,p] (the words copied), out[b,C+c,p,k] = x[b,c,idx[b,p,k]] -
+ *   query[b,c,p] (16-bit: widened, subtracted in fp32, rounded once); every element written exactly once.  The self
+ *   graph passes query = x, P = N.
+ * pp_edge_features_backward: grad_out (B,2C,P,K); grad_query (B,C,P) and grad_x (B,C,N) are overwritten, either may
+ *   be NULL (not wanted: its pass, and for grad_x the adjacency build, is skipped).
+ *   grad_query[b,c,p] = sum_k (g[b,c,p,k] - g[b,C+c,p,k]), ascending k in fp32 from the k = 0 term.
+ *   grad_x[b,c,n] = the sum of g[b,C+c,p,k] over the edges with idx[b,p,k] == n, a gather over the reverse adjacency
+ *   built in the workspace; no floating-point atomics.  ordered != 0: the edges in ascending p*K+k, plain fp32 sums
+ *   from +0.0 (the same bits on every run); otherwise any order, compensated fp32 sums.
+ *   self_graph != 0 (P == N, grad_query NULL): grad_x = the centre sum above, then the incoming terms added to it.
+ * An index outside [0,N) is only compared: its difference elements are NaN, its row (b,p) takes no part in grad_x and
+ *   its grad_query (self graph: grad_x) elements are NaN.
+ * Workspace: pp_edge_features_workspace_bytes(B, N, P, K, adjacency) bytes, adjacency != 0 where grad_x is wanted
+ *   (host arithmetic; 0 for a shape the entry points refuse).  PP_EINVAL for K > 128, an empty dimension, or where
+ *   P*K, B*N, B*P or B*C exceeds 2^31 - 1. */
+size_t pp_edge_features_workspace_bytes(int B, int N, int P, int K, int adjacency);
+int pp_edge_features_forward(const void* x, const void* query, const void* idx, void* out, int B, int C, int N, int P,
+                             int K, int dtype, int idx64, void* stream);
+int pp_edge_features_backward(const void* idx, const void* grad_out, void* grad_x, void* grad_query, int B, int C,
+                              int N, int P, int K, int dtype, int idx64, int self_graph, int ordered, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- mesh edge operators -------------------------------------------------------------------
  * What the reference's mesh losses (network/model_loss.py:166-308) and edge utilities (geo_operations.py:562-600) stand
  * on; contract in DESIGN.md "Mesh edge operators".  int64 indices, fp32 vertices (B,N,3).  The two builds run once per

@@ -7,6 +7,8 @@
     from pytorch_points.network.geo_operations import green_coordinates_3D, compute_face_normals_and_areas
     from pytorch_points.network.geo_operations import mean_value_coordinates
     from pytorch_points.network.pointnet2_utils import three_nn, three_interpolate
+    from pytorch_points.network.layers import DenseEdgeConv, SampledDenseEdgeConv, SharedMLP, Conv2d, Conv1d, Linear
+    from pytorch_points.network.pointnet2_modules import PointnetSAModuleMSG, PointnetSAModule, PointnetFPModule
     from pytorch_points._ext import losses, sampling, linalg
 
 -- runs unchanged with this repository on ``sys.path`` (no install call).  This module replaces

@@ -9,10 +9,15 @@ Drop-in for the reference's operator API on that path only:
         mean_value_coordinates, green_coordinates_3D, compute_face_normals_and_areas, pointUniformLaplacian, edge_vertex_indices,
         get_edge_lengths}
     pytorch_points.network.pointnet2_utils.{three_nn, three_interpolate, QueryAndGroup, GroupAll}
+    pytorch_points.network.layers.{SharedMLP, Conv2d, Conv1d, Linear, ShuffleBlock, DenseEdgeConv,
+        SampledDenseEdgeConv}
+    pytorch_points.network.pointnet2_modules.{PointnetSAModuleMSG, PointnetSAModule, PointnetFPModule}
     pytorch_points._ext.{losses, sampling, linalg}
 mean_value_coordinates_3D, mean_value_coordinates and green_coordinates_3D also accept CPU tensors and other dtypes,
 through torch compositions of their contracts (pytorch_points_amd.mvc.composition, pytorch_points_amd.mvc2d.composition,
-pytorch_points_amd.green.composition).
+pytorch_points_amd.green.composition).  The EdgeConv modules build their edge tensor with
+pytorch_points_amd.edge_features.knn_edge_features (fused HIP forward and backward for CUDA fp32, fp16 and bf16; its
+composition elsewhere).
 Host code is Python on PyTorch-ROCm (device memory, streams, torch.distributed); the kernels are
 hand-written HIP in csrc/, reached through the C ABI of libpp_hip.so (include/pp_hip.h).
 """
@@ -30,7 +35,8 @@ def install_as_pytorch_points():
     import importlib
     import sys
     names = ["", "._ext", "._ext.losses", "._ext.sampling", "._ext.linalg", ".network", ".network.model_loss",
-             ".network.operations", ".network.geo_operations", ".network.pointnet2_utils"]
+             ".network.operations", ".network.geo_operations", ".network.pointnet2_utils", ".network.layers",
+             ".network.pointnet2_modules"]
     for suffix in names:
         mod = importlib.import_module(__name__ + suffix)
         sys.modules["pytorch_points" + suffix] = mod

@@ -100,6 +100,9 @@ SIGNATURES = {
     "pp_knn_edge_lengths_backward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
     "pp_knn_laplacian_forward_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "pp_knn_laplacian_backward_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_edge_features_workspace_bytes": [_I, _I, _I, _I, _I],
+    "pp_edge_features_forward": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "pp_edge_features_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
     "pp_mesh_edges_workspace_bytes": [_I, _I, ctypes.c_longlong],
     "pp_mesh_unique_edges": [_P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
     "pp_mesh_edge_incidence": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
@@ -116,7 +119,7 @@ _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_byte
              "pp_three_nn_workspace_bytes": _c_size_t, "pp_knn_workspace_bytes": _c_size_t,
              "pp_shard_packed_bytes": _c_size_t, "pp_mvc3d_workspace_bytes": _c_size_t,
              "pp_gc3d_workspace_bytes": _c_size_t, "pp_mvc2d_workspace_bytes": _c_size_t,
-             "pp_knn_edges_workspace_bytes": _c_size_t,
+             "pp_knn_edges_workspace_bytes": _c_size_t, "pp_edge_features_workspace_bytes": _c_size_t,
              "pp_mesh_edges_workspace_bytes": _c_size_t}
 
 _lib = None

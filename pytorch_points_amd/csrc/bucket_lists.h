@@ -1,5 +1,6 @@
 // bucket_lists.h -- the one chain that builds per-vertex lists of integer codes, for knn_edges.hip (the reverse
-// adjacency of a k-NN graph) and mesh_edges.hip (unique edges, edge incidence, corner incidence).
+// adjacency of a k-NN graph), edge_features.hip (the same over a feature-space graph with its own centres) and
+// mesh_edges.hip (unique edges, edge incidence, corner incidence).
 //
 // A build has B batch elements of N vertices and up to `items` codes per batch element, each belonging to one vertex:
 //   count   the caller's kernel sizes every vertex's bucket with integer atomics (bucket_put<false>)
@@ -61,6 +62,24 @@ __device__ __forceinline__ size_t bucket_put(unsigned* __restrict__ cursor, unsi
   entries[slot] = code;
   return slot;
 }
+
+// The sum a vertex makes over its list in the gather backwards (knn_edges.hip, edge_features.hip).  ordered: plain fp32
+// additions in the order given, the contract's sequential loop.  Otherwise the order of the list is not defined
+// anyway, and the sum is compensated (Kahan): a hub point adds thousands of terms, whose plain sum would lose several
+// digits.
+struct ListSum {
+  float s, comp;
+  __device__ __forceinline__ void add(float v, bool ordered) {
+    if (ordered) {
+      s = s + v;
+    } else {
+      const float y = v - comp;
+      const float t = s + y;
+      comp = (t - s) - y;
+      s = t;
+    }
+  }
+};
 
 // exclusive scan of one chunk of kBucketScanThreads values inside a workgroup; returns the value's exclusive prefix
 // including `carry`, and leaves the chunk's total in *chunk_total (valid after the call for every thread)

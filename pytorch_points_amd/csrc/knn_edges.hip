@@ -155,22 +155,8 @@ __device__ __forceinline__ float ke_len_coef(float g, float o, int squared) {
   return o == 0.0f ? 0.0f : g / o;   // torch.norm's subgradient at a zero length
 }
 
-// The sums of the backwards.  ORDERED: plain fp32 additions in the order given, the contract's sequential loop.
-// Otherwise the order of the incoming terms is not defined anyway, and the sum is compensated (Kahan): a hub point
-// adds thousands of terms, whose plain sum would lose several digits.
-struct KeSum {
-  float s, comp;
-  __device__ __forceinline__ void add(float v, bool ordered) {
-    if (ordered) {
-      s = s + v;
-    } else {
-      const float y = v - comp;
-      const float t = s + y;
-      comp = (t - s) - y;
-      s = t;
-    }
-  }
-};
+// The sums of the backwards: plain in the ordered form, compensated otherwise (bucket_lists.h).
+using KeSum = pp::ListSum;
 
 // DS == 3: one thread per point; else one thread per (point, dimension).  The point's own edges in ascending k, then
 // its incoming list.  `out` is the forward's output (the length, or its square).
