@@ -539,6 +539,45 @@ int pp_mesh_laplacian_apply_f32(const float* x, const int* start, const int* nbr
                                 const float* weights, float* out, int B, int N, int F, int L, int mode,
                                 int shared_topology, void* stream);
 
+/* ---- mesh dihedral angles -------------------------------------------------------------------
+ * What the reference's get_normals / dihedral_angle (geo_operations.py:603-619, :775-789) and its (E,4) edge-points
+ * table (utils/geometry_utils.py:242-341) stand on; contract in DESIGN.md "Mesh dihedral angles".  int64 indices, fp32
+ * vertices (B,N,3).  The two builds run once per topology, the two step kernels per training step.
+ * pp_mesh_edge_points: faces (Bt,F,3), edges (Bt,Ecap,2) and counts (Bt) as pp_mesh_unique_edges made them ->
+ *   edge_points (Bt,Ecap,4): row e < counts[b] is [a, c, w0, w1], (a,c) = edges[e], w0 / w1 the corner opposite the
+ *   edge in the incident half-edge with the lowest / highest number 3f + j (half-edge j joins corners j and (j+1)%3);
+ *   a boundary edge has w1 == w0; every later row is -1.  nonmanifold (Bt) int32, initialised by the caller, is ORed
+ *   where an edge has more than two incident half-edges.  A half-edge with an index outside [0,n_vertices) is only
+ *   compared and takes no part (pp_mesh_unique_edges flags it).  Integer atomics only (min, max, count) in the rows
+ *   themselves: no scratch, and a result that does not depend on the order they are served in.
+ * pp_mesh_edge_points_incidence: edge_points (Bt,Ecap,4) -- any table -- and counts (Bt) -> start (Bt,n_vertices+1)
+ *   int32 and entries (Bt,4*Ecap) uint32: vertex v's slice [start[v],start[v+1]) holds 4*e + slot for every
+ *   e < counts[b] with edge_points[e,slot] == v, ascending (a boundary edge's repeated wing under both slots).  An
+ *   entry outside [0,n_vertices) is only compared, left out, and ORed into flags (Bt), which the caller has
+ *   initialised.  Scratch: pp_mesh_edges_workspace_bytes(Bt, n_vertices, 4*Ecap) bytes, and its limits.
+ * pp_mesh_dihedral_forward_f32: out (B,Ecap), with p_k = vertices[b, row[k]] in canonical order (the two ends
+ *   ascending, the two wings ascending: the value does not depend on either order, and so neither do its bits):
+ *   na = (p2-p0) x (p1-p0), nb = (p3-p1) x (p0-p1), each divided by max(|n|, 1e-12f);
+ *   d = clamp(na.nb, -1+1e-6, 1-1e-6); out = pi - acosf(d); 0 for e >= counts.  The products a*b - c*d are evaluated
+ *   with explicit fused multiply-adds (Kahan's difference of products).  shared_topology != 0: edge_points, counts and
+ *   the incidence have one batch element, read by every b.
+ * pp_mesh_dihedral_backward_f32: grad_vertices (B,N,3), overwritten: every vertex walks its slice in order, evaluates
+ *   the edge's chain again and adds its slot's term, plain fp32 sums from +0.  d(out)/d(d) = 1/sqrt((1-d)(1+d)) where
+ *   the unclamped dot lies in the closed clamp interval, 0 outside it, and 0 for an edge with a normal of length
+ *   <= 1e-12f.  Identical on every run; no floating-point atomics.
+ * A row with an index outside [0,N) reads nothing there: NaN angle, NaN added to the gradients of its in-range
+ * entries. */
+int pp_mesh_edge_points(const long long* faces, const long long* edges, const int* counts, long long* edge_points,
+                        int* nonmanifold, int Bt, int F, int Ecap, int n_vertices, void* stream);
+int pp_mesh_edge_points_incidence(const long long* edge_points, const int* counts, int* start, unsigned* entries,
+                                  int* flags, int Bt, int Ecap, int n_vertices, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int pp_mesh_dihedral_forward_f32(const float* vertices, const long long* edge_points, const int* counts, float* out,
+                                 int B, int N, int Ecap, int shared_topology, void* stream);
+int pp_mesh_dihedral_backward_f32(const float* vertices, const long long* edge_points, const int* start,
+                                  const unsigned* entries, const float* grad_out, float* grad_vertices, int B, int N,
+                                  int Ecap, int shared_topology, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -12,7 +12,8 @@
 //                  the atomics were served.
 //   incidence      edges (Bt,Ecap,2), counts -> for every vertex the list of 2*e + side over the edges e < count[b]
 //                  with edges[e,side] == v, ascending (the same chain).  The edge list may be any list: not unique,
-//                  not sorted, with self-edges.
+//                  not sorted, with self-edges.  The same build with four columns (4*e + slot) serves the edge
+//                  points of mesh_dihedral.hip.
 // and a training step is two launches:
 //   forward        out[b,e] = |v[b,edges[e,0]] - v[b,edges[e,1]]|^2 (pp::chamfer_d3: the bits of knn_edge_lengths'
 //                  squared form), one thread per edge; 0 for the padding rows
@@ -66,9 +67,10 @@ __global__ __launch_bounds__(kMeThreads) void me_half_edges_kernel(const long lo
   if (FILL) owner[slot] = mn;
 }
 
-// One thread per edge end (b, e, side), e < counts[b].  FILL = false: the vertices' degrees; FILL = true: the lists
-// receive 2*e + side.  An end outside [0, N) sets the flag and takes no part.
-template <bool FILL>
+// One thread per edge end (b, e, side), e < counts[b], of a table of COLS columns: 2 for an edge list, 4 for the edge
+// points of mesh_dihedral.hip.  FILL = false: the vertices' degrees; FILL = true: the lists receive COLS*e + side.  An
+// end outside [0, N) sets the flag and takes no part.
+template <bool FILL, int COLS>
 __global__ __launch_bounds__(kMeThreads) void me_edge_ends_kernel(const long long* __restrict__ edges,
                                                                   const int* __restrict__ counts,
                                                                   unsigned* __restrict__ cursor,
@@ -77,10 +79,10 @@ __global__ __launch_bounds__(kMeThreads) void me_edge_ends_kernel(const long lon
                                                                   int N) {
   const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
   if (x >= total) return;
-  const long long X = 2LL * Ecap;
+  const long long X = (long long)COLS * Ecap;
   const long long b = x / X;
-  const unsigned code = (unsigned)(x - b * X);   // 2*e + side
-  if ((int)(code >> 1) >= counts[b]) return;
+  const unsigned code = (unsigned)(x - b * X);   // COLS*e + side
+  if ((int)(code / (unsigned)COLS) >= counts[b]) return;
   const long long v = edges[x];
   if (v < 0 || v >= N) {
     if (!FILL) atomicOr(flags + b, 1);
@@ -417,11 +419,12 @@ extern "C" int pp_mesh_unique_edges(const long long* faces, long long* edges, in
   return PP_OK;
 }
 
-extern "C" int pp_mesh_edge_incidence(const long long* edges, const int* counts, int* inc_start, unsigned* inc_entries,
-                                      int* flags, int Bt, int Ecap, int n_vertices, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  const long long X = 2LL * (Ecap > 0 ? Ecap : 0);
-  const int N = n_vertices;
+namespace {
+// the vertex lists of a table (Bt,Ecap,COLS): pp_mesh_edge_incidence and pp_mesh_edge_points_incidence
+template <int COLS>
+int me_incidence(const long long* edges, const int* counts, int* inc_start, unsigned* inc_entries, int* flags, int Bt,
+                 int Ecap, int N, void* workspace, size_t workspace_bytes, void* stream) {
+  const long long X = (long long)COLS * (Ecap > 0 ? Ecap : 0);
   if (Ecap < 0 || !me_build_ok(Bt, N, X) || (long long)Bt * ((long long)N + 1) > 0x7fffffffLL) return PP_EINVAL;
   if (Bt == 0) return PP_OK;
   if (!inc_start) return PP_EINVAL;
@@ -434,7 +437,7 @@ extern "C" int pp_mesh_edge_incidence(const long long* edges, const int* counts,
   if (!edges || !counts || !flags) return PP_EINVAL;
   const long long total = (long long)Bt * X;
   if (N == 0) {   // every end of every counted edge is out of range: the count pass only compares and flags
-    me_edge_ends_kernel<false><<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(
+    me_edge_ends_kernel<false, COLS><<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(
         edges, counts, nullptr, nullptr, flags, total, Ecap, N);
     PP_RETURN_IF_LAUNCH_FAILED();
     return PP_OK;
@@ -446,10 +449,26 @@ extern "C" int pp_mesh_edge_incidence(const long long* edges, const int* counts,
   return pp::bucket_build(ws, L, inc_entries, inc_start, Bt, N, X, true, s, [&](bool fill) {
     const dim3 grid(pp::blocks(total, kMeThreads)), block(kMeThreads);
     if (fill)
-      me_edge_ends_kernel<true><<<grid, block, 0, s>>>(edges, counts, cursor, inc_entries, flags, total, Ecap, N);
+      me_edge_ends_kernel<true, COLS><<<grid, block, 0, s>>>(edges, counts, cursor, inc_entries, flags, total, Ecap, N);
     else
-      me_edge_ends_kernel<false><<<grid, block, 0, s>>>(edges, counts, cursor, inc_entries, flags, total, Ecap, N);
+      me_edge_ends_kernel<false, COLS><<<grid, block, 0, s>>>(edges, counts, cursor, inc_entries, flags, total, Ecap, N);
   });
+}
+}  // namespace
+
+extern "C" int pp_mesh_edge_incidence(const long long* edges, const int* counts, int* inc_start, unsigned* inc_entries,
+                                      int* flags, int Bt, int Ecap, int n_vertices, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return me_incidence<2>(edges, counts, inc_start, inc_entries, flags, Bt, Ecap, n_vertices, workspace, workspace_bytes,
+                         stream);
+}
+
+// the (E,4) edge points of mesh_dihedral.hip: vertex v's list holds 4*e + slot
+extern "C" int pp_mesh_edge_points_incidence(const long long* edge_points, const int* counts, int* start,
+                                             unsigned* entries, int* flags, int Bt, int Ecap, int n_vertices,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return me_incidence<4>(edge_points, counts, start, entries, flags, Bt, Ecap, n_vertices, workspace, workspace_bytes,
+                         stream);
 }
 
 extern "C" int pp_mesh_edge_sqrlen_forward_f32(const float* vertices, const long long* edges, const int* counts,

@@ -4,8 +4,10 @@ furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point
 polygon cage) and green_coordinates_3D (:625-773), and the
 face normals those need, compute_face_normals_and_areas (:529-559), the point-cloud Laplacian
 pointUniformLaplacian (:128-152), the mesh Laplacians UniformLaplacian, CotLaplacian and cotangent (:155-346), and
-the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600).
-The remaining names of that file do not work in the reference either."""
+the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600), and the face-to-face angles get_normals
+(:603-619, without its stray check_values line) and dihedral_angle (:775-789) with the (E,4) table they work on,
+get_edge_points (utils/geometry_utils.py:242-341: build_gemm, get_edge_points, get_side_points).
+Only green_coordinates_2D, an empty stub in the reference, stays out."""
 import collections
 
 import numpy as np
@@ -13,6 +15,7 @@ import torch
 
 from .. import green as _green
 from .. import knn_edges as _knn_edges
+from .. import mesh_dihedral as _mesh_dihedral
 from .. import mesh_edges as _mesh_edges
 from .. import mesh_laplacian as _mesh_laplacian
 from .. import mvc as _mvc
@@ -201,6 +204,70 @@ def get_edge_lengths(vertices, edge_points):
     ends = vertices[edge_points[:, :2]]
     t = ends[:, 0, :] - ends[:, 1, :]
     return torch.sum(t * t, dim=-1)
+
+
+# -------------------------------------------------------------------------------------- mesh dihedral angles
+def get_edge_points(faces_or_mesh, n_vertices=None):
+    """The ``(E,4)`` int64 table ``[a, c, w0, w1]`` of a triangle mesh (reference utils/geometry_utils.py:242-341,
+    there a Python loop over the faces): ``(a,c)`` the unique edges in ``edge_vertex_indices``' order, ``w0`` / ``w1``
+    the corners opposite the edge in its incident half-edge with the lowest / highest number ``3*f + j``, ``w1 == w0``
+    on a boundary edge (the reference's ``get_side_points`` there).  ``faces_or_mesh``: a ``(F,3)`` tensor or array,
+    or any object with ``fs`` (and ``vs`` for the vertex count); a tensor gives a tensor on its device, anything else
+    a numpy array.  The reference's column order follows its face traversal; ``dihedral_angle`` does not depend on it.
+    An edge with more than two incident half-edges raises ValueError (the reference's ``build_gemm``: IndexError), an
+    index outside ``[0, n_vertices)`` IndexError.  ``n_vertices`` defaults to ``faces.max() + 1`` (on CUDA a second
+    host read beside the build's own).  For a loop that keeps its topology, build a
+    ``pytorch_points_amd.mesh_dihedral.MeshEdgePoints`` once instead."""
+    faces = faces_or_mesh
+    if hasattr(faces_or_mesh, "fs"):
+        faces = faces_or_mesh.fs
+        if n_vertices is None and getattr(faces_or_mesh, "vs", None) is not None:
+            n_vertices = len(faces_or_mesh.vs)
+    as_tensor = isinstance(faces, torch.Tensor)
+    if not as_tensor:
+        faces = torch.from_numpy(np.ascontiguousarray(np.asarray(faces)))
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise NotImplementedError("get_edge_points: faces must have shape (F, 3) (triangles), got %s"
+                                  % (tuple(faces.shape),))
+    if not _mesh_edges._is_index(faces):
+        raise TypeError("get_edge_points: faces must be integers, got %s" % faces.dtype)
+    if faces.shape[0] == 0:
+        table = faces.new_empty((0, 4), dtype=torch.int64)
+    else:
+        if n_vertices is None:
+            n_vertices = max(int(faces.max()) + 1, 0)
+        table = _mesh_dihedral.MeshEdgePoints.from_faces(faces, n_vertices).table(0)
+    return table if as_tensor else table.numpy()
+
+
+def get_normals(vertices, edge_points, side):
+    """The unit normal ``(E,3)`` of the face on one side of every edge (reference :603-619, without the
+    ``check_values`` line it dies on): ``vertices`` (N,3), ``edge_points`` (E,4), ``side`` 0-3 -- sides 0, 1 the face
+    with column 2 seen from column 0, sides 2, 3 the face with column 3 seen from column 1.  Torch operations."""
+    base, other, wing = (0, 1, 2) if side < 2 else (1, 0, 3)        # the face (base, other end, wing), seen from base
+    origin = vertices[edge_points[:, base]]
+    to_wing = vertices[edge_points[:, wing]] - origin
+    along = vertices[edge_points[:, other]] - origin
+    return torch.nn.functional.normalize(torch.cross(to_wing, along, dim=-1), dim=-1)
+
+
+def dihedral_angle(vertices, edge_points):
+    """The face-to-face angle ``(E,)`` across the edges given by their four ``edge_points`` (E,4) over ``vertices``
+    (N,3): ``pi - acos(clamp(n_a . n_b, -1+1e-6, 1-1e-6))`` (reference :775-789).  CUDA fp32 runs the HIP kernels; the
+    backward builds the table's vertex lists when, and only when, a gradient is asked for.  Nothing synchronises with
+    the host: on that path an index outside [0, N) gives a NaN angle (the reference wraps a negative index and faults
+    on a large one).  Other devices and dtypes: ``pytorch_points_amd.mesh_dihedral.dihedral_composition``, with an
+    IndexError for such an index on the CPU."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or edge_points.dim() != 2 or edge_points.shape[1] != 4:
+        raise ValueError("dihedral_angle: vertices (N, 3) and edge_points (E, 4), got %s and %s"
+                         % (tuple(vertices.shape), tuple(edge_points.shape)))
+    if not _mesh_edges._is_index(edge_points):
+        raise TypeError("dihedral_angle: edge_points must be an integer tensor, got %s" % edge_points.dtype)
+    if edge_points.is_cuda:
+        topo = _mesh_dihedral.MeshEdgePoints._unchecked(edge_points.long().contiguous().unsqueeze(0), vertices.shape[0])
+    else:
+        topo = _mesh_dihedral.MeshEdgePoints.from_edge_points(edge_points, vertices.shape[0])
+    return _mesh_dihedral.mesh_dihedral_angle(vertices.unsqueeze(0), topo)[0]
 
 
 # ------------------------------------------------------------------------------------------- mesh Laplacians

@@ -15,6 +15,7 @@ import torch
 
 from .. import _lib
 from .. import knn_edges as _knn_edges
+from .. import mesh_dihedral as _mesh_dihedral
 from .. import mesh_edges as _mesh_edges
 from .. import ops
 from .._ext import losses
@@ -409,6 +410,43 @@ class SimpleMeshRepulsionLoss(torch.nn.Module):
         tmp = 1 / (sq + 1e-6)
         tmp = torch.where(sq < self.threshold2, tmp, torch.zeros_like(tmp))
         return _reduce_edges(tmp, topo, self.reduction)
+
+
+class MeshDihedralAngleLoss(torch.nn.Module):
+    """A bending / fold-over penalty on the face-to-face angles of a triangle mesh
+    (``pytorch_points_amd.mesh_dihedral.mesh_dihedral_angle``: ``pi`` less the angle between the two face normals at
+    an edge, the interior angle of a consistently oriented mesh: a flat edge is near ``pi``, a sharp fold near 0).
+    The reference has no such module; the signature follows its mesh losses.  ``vert1`` (B,N,3), ``face`` (B,F,3):
+
+    * with ``vert2`` (B,N,3): ``(angle(vert1) - angle(vert2)) ** 2`` per edge;
+    * without: ``relu(threshold - angle(vert1)) ** 2``, which penalises the edges folded below ``threshold``.
+
+    Boundary edges have a constant angle and no gradient.  Per batch element ``mean`` / ``max`` / ``sum`` over its own
+    edges, then the mean over the batch; ``"none"``: the (B,) means.  ``self.E`` is the ``MeshEdgePoints`` of the last
+    build; it is kept, and never checked against later faces, while ``consistent_topology`` is set."""
+
+    def __init__(self, threshold=None, reduction="mean", consistent_topology=False):
+        super().__init__()
+        self.threshold = threshold
+        self.reduction = reduction
+        self.consistent_topology = consistent_topology
+        self.E = None
+
+    def forward(self, vert1, vert2=None, face=None):
+        if self.reduction not in ("mean", "none", "max", "sum"):
+            raise NotImplementedError
+        if (not self.consistent_topology) or (self.E is None):
+            assert(face is not None), "Face is required"
+            self.E = _mesh_dihedral.MeshEdgePoints.from_faces(face, vert1.shape[1])
+        topo = self.E
+        angle1 = _mesh_dihedral.mesh_dihedral_angle(vert1, topo)
+        if vert2 is not None:
+            assert(vert1.shape == vert2.shape)
+            diff = angle1 - _mesh_dihedral.mesh_dihedral_angle(vert2, topo)
+        else:
+            assert(self.threshold is not None), "threshold is required without vert2"
+            diff = torch.relu(self.threshold - angle1)
+        return _reduce_edges(diff * diff, topo, self.reduction)
 
 
 # ---------------------------------------------------------------------------------------- mesh Laplacian losses
