@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from pytorch_points_amd import edge_features, ops, synthetic
 from pytorch_points_amd.network import geo_operations, layers, operations, pointnet2_modules, pointnet2_utils
+from topology_fuzz import np_ef_backward as np_backward, np_ef_forward as np_forward, round_to
 
 pytestmark = pytest.mark.gpu
 
@@ -29,19 +30,6 @@ CS = [1, 3, 24, 65]
 
 
 # ------------------------------------------------------------------------------------------------ numpy side
-def round_to(a, dtype):
-    """fp32 array -> the nearest values of ``dtype`` (ties to even), held in fp32"""
-    a = np.ascontiguousarray(a, dtype=F32)
-    if dtype is torch.float32:
-        return a
-    if dtype is torch.float16:
-        with np.errstate(over="ignore"):
-            return a.astype(np.float16).astype(F32)
-    u = a.view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7fff + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32).reshape(a.shape)
-
-
 def bits(a):
     return np.ascontiguousarray(a, dtype=F32).view(np.uint32)
 
@@ -49,29 +37,6 @@ def bits(a):
 def same_bits(got, want):
     """a torch tensor of any of the three types against an fp32 array of that type's values (widening is exact)"""
     return np.array_equal(bits(got.detach().float().cpu().numpy()), bits(want))
-
-
-def np_forward(x, idx, q, dtype):
-    b = np.arange(x.shape[0])[:, None, None, None]
-    c = np.arange(x.shape[1])[None, :, None, None]
-    centre = np.broadcast_to(q[..., None], q.shape + (idx.shape[2],))
-    return np.concatenate([centre, round_to(x[b, c, idx[:, None]] - centre, dtype)], axis=1)
-
-
-def np_backward(g, idx, n, self_graph, dtype):
-    """(grad_x, grad_query) of the ordered form: the centre sums in ascending k from the k = 0 term; grad_x from +0.0
-    (the self graph: from the centre sum) with the incoming terms in ascending (p, k), as np.add.at applies them; fp32
-    throughout, one rounding to ``dtype`` at the end"""
-    c = g.shape[1] // 2
-    gc, gd = g[:, :c], g[:, c:]
-    t = gc - gd
-    gq = t[..., 0]
-    for k in range(1, g.shape[3]):
-        gq = gq + t[..., k]
-    gx = gq.transpose(0, 2, 1).copy() if self_graph else np.zeros((g.shape[0], n, c), F32)
-    for b in range(g.shape[0]):
-        np.add.at(gx[b], idx[b].reshape(-1), gd[b].reshape(c, -1).T)
-    return round_to(gx.transpose(0, 2, 1), dtype), round_to(gq, dtype)
 
 
 def by_row(a):

@@ -12,6 +12,7 @@ import torch
 import oracle
 from pytorch_points_amd import knn_edges, ops, synthetic
 from pytorch_points_amd.network import geo_operations, model_loss
+from topology_fuzz import np_lap_backward, np_laplacian, np_len_backward
 
 pytestmark = pytest.mark.gpu
 
@@ -35,38 +36,6 @@ def searched(b, n, k):
     p = cloud(b, n)
     res = ops.knn_points(dev_t(p, "cuda"), dev_t(p, "cuda"), K=k + 1)
     return p, res.idx[:, :, 1:].cpu().numpy(), res.dists[:, :, 1:].cpu().numpy()
-
-
-def np_laplacian(p, idx):
-    b = np.arange(p.shape[0])[:, None]
-    total = p[b, idx[:, :, 0]]
-    for k in range(1, idx.shape[2]):
-        total = total + p[b, idx[:, :, k]]
-    return -(total / F32(idx.shape[2])) + p
-
-
-def np_len_backward(p, idx, out, g, squared, detach=False):
-    """every point's own edges in ascending k, then the incoming edges in ascending (n, k): fp32, one rounding per
-    operation (np.subtract.at applies its operands one after the other, in index order)"""
-    bb = np.arange(p.shape[0])[:, None, None]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        coef = F32(2) * g if squared else np.where(out == 0, F32(0), g / out).astype(F32)
-    term = coef[..., None] * (p[:, :, None, :] - p[bb, idx])
-    grad = np.zeros_like(p)
-    for k in range(idx.shape[2]):
-        grad = grad + term[:, :, k]
-    if not detach:
-        for b in range(p.shape[0]):
-            np.subtract.at(grad[b], idx[b].reshape(-1), term[b].reshape(-1, p.shape[2]))
-    return grad
-
-
-def np_lap_backward(idx, g):
-    grad = g.copy()
-    k = idx.shape[2]
-    for b in range(g.shape[0]):
-        np.subtract.at(grad[b], idx[b].reshape(-1), np.repeat(g[b] / F32(k), k, axis=0))
-    return grad
 
 
 def measure(got, ref):

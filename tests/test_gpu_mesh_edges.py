@@ -14,6 +14,7 @@ from pytorch_points_amd import knn_edges, mesh_edges, synthetic
 from pytorch_points_amd.network import geo_operations, model_loss
 from test_mesh_edges_host import (REDUCTIONS, fan_mesh, grid_mesh, jittered_grid, np_unique_edges, soup_mesh,
                                   tetrahedron)
+from topology_fuzz import np_backward
 
 pytestmark = pytest.mark.gpu
 
@@ -164,17 +165,6 @@ def test_forward_bit_equal_to_knn_edge_lengths(cuda, name):
 
 
 # ----------------------------------------------------------------------------------------------- 4. backward
-def np_backward(verts, edges_of, g):
-    """the sequential fp32 loop `for e: grad[a] += t_e; grad[b] -= t_e`, t_e = (2 g_e) (v_a - v_b): np.add.at applies
-    its operands one after the other, in index order"""
-    grad = np.zeros_like(verts)
-    for b in range(verts.shape[0]):
-        e = edges_of(b)
-        t = (F32(2) * g[b, :e.shape[0]])[:, None] * (verts[b, e[:, 0]] - verts[b, e[:, 1]])
-        np.add.at(grad[b], e.reshape(-1), np.stack([t, -t], 1).reshape(-1, 3))
-    return grad
-
-
 @contextlib.contextmanager
 def deterministic():
     torch.use_deterministic_algorithms(True)

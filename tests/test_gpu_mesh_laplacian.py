@@ -14,6 +14,7 @@ from pytorch_points_amd import mesh_laplacian, synthetic
 from pytorch_points_amd.network import geo_operations, model_loss
 from test_mesh_edges_host import fan_mesh, grid_mesh, jittered_grid, soup_mesh
 from test_mesh_laplacian_host import quad_grid, with_isolated_vertex
+from topology_fuzz import np_apply, np_corners
 
 pytestmark = pytest.mark.gpu
 
@@ -45,17 +46,6 @@ def two_topologies():
     """grid 9x11 and a soup over the same 99 vertices, 160 faces each"""
     fa = grid_mesh(9, 11)[1]
     return np.stack([fa, soup_mesh(99, fa.shape[0], 5)[0]])
-
-
-def np_corners(faces, n):
-    """(start (n+1,) int32, codes (L*F,) int32, nbr (L*F,2) int32) of one mesh: a stable sort of the corner keys"""
-    deg = faces.shape[1]
-    flat = faces.reshape(-1)
-    codes = np.argsort(flat, kind="stable")
-    start = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=n))])
-    f, c = codes // deg, codes % deg
-    nbr = np.stack([faces[f, (c + 1) % deg], faces[f, (c - 1) % deg]], -1)
-    return start.astype(np.int32), codes.astype(np.int32), nbr.astype(np.int32)
 
 
 def assert_corners(corners, b, faces, n):
@@ -154,29 +144,6 @@ def test_cotangent_kernel(cuda):
 
 
 # ------------------------------------------------------------------------------------------------ 3. applies
-def np_apply(x, start, nbr, codes, weights, mode):
-    """The sequential fp32 loop of one batch element: every vertex's slice in ascending slot order from +0, slot k of
-    every vertex at once (numpy's fp32 operations are the kernel's: IEEE, one rounding each).  mode 0: uniform
-    forward; 1: uniform backward on the gradient x; 2: cotangent with weights (F,3)."""
-    count = (start[1:] - start[:-1]).astype(np.int64)
-    div = ((2 * count).astype(F32) + F32(1e-12))[:, None]
-    h = (x / div).astype(F32) if mode == 1 else x
-    acc = np.zeros_like(x)
-    for k in range(int(count.max(initial=0))):
-        vs = np.flatnonzero(count > k)
-        q = start[vs] + k
-        for side in (0, 1):
-            other = h[nbr[q, side]]
-            if mode == 2:
-                f, c = codes[q] // 3, codes[q] % 3
-                w = weights[f, (c + 2) % 3 if side == 0 else (c + 1) % 3][:, None]
-                acc[vs] = acc[vs] + w * (other - h[vs])
-            else:
-                acc[vs] = acc[vs] + (h[vs] - other)
-    assert acc.dtype == F32
-    return (acc / div).astype(F32) if mode == 0 else acc
-
-
 def np_apply_batch(x, faces, n, weights, mode):
     out = []
     for b in range(x.shape[0]):
