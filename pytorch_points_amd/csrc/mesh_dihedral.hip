@@ -27,7 +27,7 @@
 //
 // An index outside [0, n_vertices) is never used as an address: the builds compare it and leave out what it belongs
 // to, the forward writes NaN for such an edge and the backward adds NaN for it.
-#include "bucket_lists.h"   // pp::blocks, pp::quiet_nan
+#include "mesh_common.h"   // pp::mesh_half_edge, pp::mesh_build_ok; pp::blocks, pp::quiet_nan
 
 namespace {
 
@@ -59,13 +59,9 @@ __global__ __launch_bounds__(kMdThreads) void md_half_edges_kernel(const long lo
                                                                    long long total, int F, int Ecap, int N) {
   const long long h = (long long)blockIdx.x * kMdThreads + threadIdx.x;
   if (h >= total) return;
-  const long long H = 3LL * F;
-  const long long b = h / H;
-  const long long f = h / 3;          // face number over the whole batch
-  const int j = (int)(h - f * 3);
-  const long long p = faces[f * 3 + j], q = faces[f * 3 + (j == 2 ? 0 : j + 1)];
-  if (p < 0 || p >= N || q < 0 || q >= N) return;
-  const long long mn = p < q ? p : q, mx = p < q ? q : p;
+  const pp::MeshHalfEdge he = pp::mesh_half_edge(faces, h, F, N);
+  if (!he.in_range) return;
+  const long long b = he.b, mn = he.mn, mx = he.mx;
   const long long* __restrict__ eb = edges + b * Ecap * 2;
   int count = counts[b];
   count = count < 0 ? 0 : (count > Ecap ? Ecap : count);
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(kMdThreads) void md_half_edges_kernel(const long lo
   }
   if (lo >= count || eb[2 * (size_t)lo] != mn || eb[2 * (size_t)lo + 1] != mx) return;
   unsigned* w = reinterpret_cast<unsigned*>(edge_points + (b * Ecap + lo) * 4);
-  const unsigned code = (unsigned)(h - b * H);   // 3*f + j within the batch element
+  const unsigned code = (unsigned)(h - b * 3LL * F);   // 3*f + j within the batch element
   atomicMin(w, code);
   atomicMax(w + 1, code);
   atomicAdd(w + 2, 1u);
@@ -272,19 +268,15 @@ __global__ __launch_bounds__(kMdThreads) void md_backward_kernel(
   grad[i * 3 + 2] = az;
 }
 
-// the index words in use, as in mesh_edges.hip
-bool md_build_ok(int Bt, int N, long long items) {
-  return Bt >= 0 && N >= 0 && items >= 0 && (long long)Bt * items <= 0x7fffffffLL &&
-         (long long)Bt * ((long long)N + 1) <= 0x7fffffffLL;
-}
-
 }  // namespace
 
 extern "C" int pp_mesh_edge_points(const long long* faces, const long long* edges, const int* counts,
                                    long long* edge_points, int* nonmanifold, int Bt, int F, int Ecap, int n_vertices,
                                    void* stream) {
   const long long H = 3LL * (F > 0 ? F : 0);
-  if (F < 0 || Ecap < 0 || !md_build_ok(Bt, n_vertices, H) || !md_build_ok(Bt, n_vertices, 4LL * Ecap)) return PP_EINVAL;
+  if (F < 0 || Ecap < 0 || !pp::mesh_build_ok(Bt, n_vertices, H, true) ||
+      !pp::mesh_build_ok(Bt, n_vertices, 4LL * Ecap, true))
+    return PP_EINVAL;
   if (Bt == 0 || Ecap == 0) return PP_OK;
   if (!edges || !counts || !edge_points || !nonmanifold || (F > 0 && !faces)) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;

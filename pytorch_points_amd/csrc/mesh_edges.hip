@@ -33,7 +33,7 @@
 //   apply              one thread per (b, vertex): a gather over the vertex's slice from +0 in slot order, plain fp32
 //                      operations; the uniform operator's forward and backward and the cotangent operator (whose
 //                      backward is the same call on the gradient) are three modes of one kernel
-#include "bucket_lists.h"
+#include "mesh_common.h"
 
 namespace {
 
@@ -53,23 +53,19 @@ __global__ __launch_bounds__(kMeThreads) void me_half_edges_kernel(const long lo
                                                                    int N) {
   const long long h = (long long)blockIdx.x * kMeThreads + threadIdx.x;
   if (h >= total) return;
-  const long long H = 3LL * F;
-  const long long b = h / H;
-  const long long f = h / 3;          // face number over the whole batch
-  const int j = (int)(h - f * 3);
-  const long long p = faces[f * 3 + j], q = faces[f * 3 + (j == 2 ? 0 : j + 1)];
-  if (p < 0 || p >= N || q < 0 || q >= N) {
-    if (!FILL) atomicOr(flags + b, 1);
+  const pp::MeshHalfEdge e = pp::mesh_half_edge(faces, h, F, N);
+  if (!e.in_range) {
+    if (!FILL) atomicOr(flags + e.b, 1);
     return;
   }
-  const unsigned mn = (unsigned)(p < q ? p : q), mx = (unsigned)(p < q ? q : p);
-  const size_t slot = pp::bucket_put<FILL>(cursor, entries, b, N, H, mn, mx);
-  if (FILL) owner[slot] = mn;
+  const size_t slot = pp::bucket_put<FILL>(cursor, entries, e.b, N, 3LL * F, (unsigned)e.mn, (unsigned)e.mx);
+  if (FILL) owner[slot] = (unsigned)e.mn;
 }
 
 // One thread per edge end (b, e, side), e < counts[b], of a table of COLS columns: 2 for an edge list, 4 for the edge
-// points of mesh_dihedral.hip.  FILL = false: the vertices' degrees; FILL = true: the lists receive COLS*e + side.  An
-// end outside [0, N) sets the flag and takes no part.
+// points of mesh_dihedral.hip, 1 for the corners of faces (Bt,F,L) taken as L*F rows.  Without counts (a null pointer,
+// the same for every thread) all rows count.  FILL = false: the vertices' degrees; FILL = true: the lists receive
+// COLS*e + side.  An end outside [0, N) sets the flag and takes no part.
 template <bool FILL, int COLS>
 __global__ __launch_bounds__(kMeThreads) void me_edge_ends_kernel(const long long* __restrict__ edges,
                                                                   const int* __restrict__ counts,
@@ -82,7 +78,7 @@ __global__ __launch_bounds__(kMeThreads) void me_edge_ends_kernel(const long lon
   const long long X = (long long)COLS * Ecap;
   const long long b = x / X;
   const unsigned code = (unsigned)(x - b * X);   // COLS*e + side
-  if ((int)(code / (unsigned)COLS) >= counts[b]) return;
+  if (counts != nullptr && (int)(code / (unsigned)COLS) >= counts[b]) return;
   const long long v = edges[x];
   if (v < 0 || v >= N) {
     if (!FILL) atomicOr(flags + b, 1);
@@ -200,25 +196,7 @@ __global__ __launch_bounds__(kMeThreads) void me_sqrlen_backward_kernel(
 }
 
 // ---- corners ------------------------------------------------------------------------------------------------------
-// One thread per corner (b, f, c) of faces (Bt,F,L).  FILL = false: the vertices' corner counts; FILL = true: the lists
-// receive L*f + c.  A corner outside [0, N) sets the flag and takes no part.
-template <bool FILL>
-__global__ __launch_bounds__(kMeThreads) void me_corners_kernel(const long long* __restrict__ faces,
-                                                                unsigned* __restrict__ cursor,
-                                                                unsigned* __restrict__ entries,
-                                                                int* __restrict__ flags, long long total,
-                                                                long long X, int N) {
-  const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
-  if (x >= total) return;
-  const long long b = x / X;
-  const long long v = faces[x];
-  if (v < 0 || v >= N) {
-    if (!FILL) atomicOr(flags + b, 1);
-    return;
-  }
-  pp::bucket_put<FILL>(cursor, entries, b, N, X, (size_t)v, (unsigned)(x - b * X));
-}
-
+// (their lists are me_edge_ends_kernel's with one column)
 // One thread per slot of the sorted lists: (next, prev) of the slot's corner, -1 for a vertex outside [0, N), so that
 // the apply reads its neighbours beside each other and never follows a 64-bit face row
 __global__ __launch_bounds__(kMeThreads) void me_corner_nbr_kernel(const long long* __restrict__ faces,
@@ -368,15 +346,10 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-// the index words in use: u32 positions and codes within a batch element, int32 starts, 31-bit grids
-bool me_build_ok(int Bt, int N, long long items) {
-  return Bt >= 0 && N >= 0 && items >= 0 && (long long)Bt * items <= 0x7fffffffLL && (long long)Bt * N <= 0x7fffffffLL;
-}
-
 }  // namespace
 
 extern "C" size_t pp_mesh_edges_workspace_bytes(int Bt, int n_vertices, long long items) {
-  if (Bt <= 0 || n_vertices <= 0 || items <= 0 || !me_build_ok(Bt, n_vertices, items)) return 0;
+  if (Bt <= 0 || n_vertices <= 0 || items <= 0 || !pp::mesh_build_ok(Bt, n_vertices, items, false)) return 0;
   return pp::bucket_layout(Bt, n_vertices, items, true).total;
 }
 
@@ -384,7 +357,7 @@ extern "C" int pp_mesh_unique_edges(const long long* faces, long long* edges, in
                                     int n_vertices, void* workspace, size_t workspace_bytes, void* stream) {
   const long long H = 3LL * (F > 0 ? F : 0);
   const int N = n_vertices;
-  if (F < 0 || !me_build_ok(Bt, N, H)) return PP_EINVAL;
+  if (F < 0 || !pp::mesh_build_ok(Bt, N, H, false)) return PP_EINVAL;
   if (Bt == 0) return PP_OK;
   if (!counts || !flags) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -420,12 +393,13 @@ extern "C" int pp_mesh_unique_edges(const long long* faces, long long* edges, in
 }
 
 namespace {
-// the vertex lists of a table (Bt,Ecap,COLS): pp_mesh_edge_incidence and pp_mesh_edge_points_incidence
+// the vertex lists of a table (Bt,Ecap,COLS): pp_mesh_edge_incidence, pp_mesh_edge_points_incidence and, with one
+// column and no counts, pp_mesh_corner_incidence
 template <int COLS>
 int me_incidence(const long long* edges, const int* counts, int* inc_start, unsigned* inc_entries, int* flags, int Bt,
                  int Ecap, int N, void* workspace, size_t workspace_bytes, void* stream) {
   const long long X = (long long)COLS * (Ecap > 0 ? Ecap : 0);
-  if (Ecap < 0 || !me_build_ok(Bt, N, X) || (long long)Bt * ((long long)N + 1) > 0x7fffffffLL) return PP_EINVAL;
+  if (Ecap < 0 || !pp::mesh_build_ok(Bt, N, X, true)) return PP_EINVAL;
   if (Bt == 0) return PP_OK;
   if (!inc_start) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -434,7 +408,7 @@ int me_incidence(const long long* edges, const int* counts, int* inc_start, unsi
     if (e != hipSuccess) return (int)e;
     if (Ecap == 0) return PP_OK;
   }
-  if (!edges || !counts || !flags) return PP_EINVAL;
+  if (!edges || (!counts && COLS != 1) || !flags) return PP_EINVAL;
   const long long total = (long long)Bt * X;
   if (N == 0) {   // every end of every counted edge is out of range: the count pass only compares and flags
     me_edge_ends_kernel<false, COLS><<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(
@@ -499,37 +473,23 @@ extern "C" int pp_mesh_edge_sqrlen_backward_f32(const float* vertices, const lon
   return PP_OK;
 }
 
+// the corners (b, f, c) of faces (Bt,F,L) are the L*F rows of a one-column table: vertex v's list holds L*f + c
 extern "C" int pp_mesh_corner_incidence(const long long* faces, int* start, unsigned* codes, int* nbr, int* flags,
                                         int Bt, int F, int L, int n_vertices, void* workspace, size_t workspace_bytes,
                                         void* stream) {
   const int N = n_vertices;
-  if (F < 0 || L < 3) return PP_EINVAL;
   const long long X = (long long)L * F;
-  if (!me_build_ok(Bt, N, X) || (long long)Bt * ((long long)N + 1) > 0x7fffffffLL) return PP_EINVAL;
+  if (F < 0 || L < 3 || !pp::mesh_build_ok(Bt, N, X, true)) return PP_EINVAL;
   if (Bt == 0) return PP_OK;
-  if (!start || !flags) return PP_EINVAL;
+  const bool listed = F > 0 && N > 0;   // else no list has an entry (a corner of a mesh without vertices is flagged)
+  if (!start || !flags || (listed && !nbr)) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = pp::fill_bytes(flags, 0, 4 * (size_t)Bt, s);
+  const hipError_t e = pp::fill_bytes(flags, 0, 4 * (size_t)Bt, s);
   if (e != hipSuccess) return (int)e;
-  if (F == 0 || N == 0) {   // no list has an entry; a corner of a mesh without vertices is out of range
-    e = pp::fill_bytes(start, 0, 4 * (size_t)Bt * ((size_t)N + 1), s);
-    if (e != hipSuccess) return (int)e;
-    if (F == 0) return PP_OK;
-    return (int)pp::fill_bytes(flags, 1, 4 * (size_t)Bt, s);   // (any non-zero word)
-  }
-  const pp::BucketLayout lay = pp::bucket_layout(Bt, N, X, false);
-  unsigned char* ws = (unsigned char*)workspace;
-  if (!faces || !codes || !nbr || !ws || workspace_bytes < lay.entries) return PP_EINVAL;   // the lists are built in place
-  unsigned* cursor = reinterpret_cast<unsigned*>(ws + lay.cursor);
+  const int rc = me_incidence<1>(faces, nullptr, start, codes, flags, Bt, (int)X, N, workspace, workspace_bytes,
+                                 stream);
+  if (rc != PP_OK || !listed) return rc;
   const long long total = (long long)Bt * X;
-  const int rc = pp::bucket_build(ws, lay, codes, start, Bt, N, X, true, s, [&](bool fill) {
-    const dim3 grid(pp::blocks(total, kMeThreads)), block(kMeThreads);
-    if (fill)
-      me_corners_kernel<true><<<grid, block, 0, s>>>(faces, cursor, codes, flags, total, X, N);
-    else
-      me_corners_kernel<false><<<grid, block, 0, s>>>(faces, cursor, codes, flags, total, X, N);
-  });
-  if (rc != PP_OK) return rc;
   me_corner_nbr_kernel<<<dim3(pp::blocks(total, kMeThreads)), dim3(kMeThreads), 0, s>>>(faces, start, codes, nbr, total,
                                                                                         X, L, N);
   PP_RETURN_IF_LAUNCH_FAILED();

@@ -10,16 +10,18 @@ device-to-host copy) and kept; a step on it is two launches and never synchronis
 HIP kernels of csrc/mesh_dihedral.hip (``pp_mesh_edge_points*``, ``pp_mesh_dihedral_*``): a backward that is a gather
 over each vertex's sorted list of table entries -- no floating-point atomics, the same bits on every run, one form
 only.  CPU tensors and other dtypes go through ``dihedral_composition``, the same contract written as torch
-operations.  DESIGN.md "Mesh dihedral angles" states the contract.
+operations.  ``MeshEdgePoints`` is ``_mesh_topology``'s counted row table with four columns and the step its
+``gather_function``; here are the table's build chain and the composition.  DESIGN.md "Mesh dihedral angles" states
+the contract.
 """
 import math
 
 import torch
 
 from . import _lib
+from . import _mesh_topology as _topology
 from . import mesh_edges as _mesh_edges
 
-_LIMIT = _mesh_edges._LIMIT
 _EPS = 1e-12                      # F.normalize's eps
 _LO, _HI = -1 + 1e-6, 1 - 1e-6    # the reference's clamp
 
@@ -29,29 +31,13 @@ def _edge_points_hip(faces, edges, counts, nonmanifold, n_vertices):
     ``edge_points`` (Bt,Ecap,4); an edge with more than two half-edges is ORed into ``nonmanifold`` (Bt, initialised)"""
     dev = faces.device
     bt, f, ecap = faces.shape[0], faces.shape[1], edges.shape[1]
-    _mesh_edges._fits("edge points", bt, n_vertices, 4 * ecap)
+    _topology.fits("edge points", bt, n_vertices, 4 * ecap)
     edge_points = torch.empty(bt, ecap, 4, dtype=torch.int64, device=dev)
     with _lib.on_device(dev) as stream:
         _lib.check(_lib.lib().pp_mesh_edge_points(_lib.ptr(faces), _lib.ptr(edges), _lib.ptr(counts),
                                                   _lib.ptr(edge_points), _lib.ptr(nonmanifold), bt, f, ecap,
                                                   n_vertices, stream), "mesh edge points")
     return edge_points
-
-
-def _incidence_hip(edge_points, counts, n_vertices, flags):
-    """contiguous int64 CUDA ``edge_points`` (Bt,Ecap,4), int32 ``counts`` (Bt) -> ``(start (Bt,N+1) int32, entries
-    (Bt,4*Ecap) as int32 storage)``; an out-of-range entry is ORed into ``flags`` (Bt, initialised)."""
-    dev = edge_points.device
-    bt, ecap = edge_points.shape[0], edge_points.shape[1]
-    _mesh_edges._fits("edge-points incidence", bt, n_vertices, 4 * ecap)
-    start = torch.empty(bt, n_vertices + 1, dtype=torch.int32, device=dev)
-    entries = torch.empty(bt, 4 * ecap, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev) as stream:
-        wsp, nbytes, ws = _mesh_edges._workspace(dev, bt, n_vertices, 4 * ecap)
-        _lib.check(_lib.lib().pp_mesh_edge_points_incidence(_lib.ptr(edge_points), _lib.ptr(counts), _lib.ptr(start),
-                                                            _lib.ptr(entries), _lib.ptr(flags), bt, ecap, n_vertices,
-                                                            wsp, nbytes, stream), "mesh edge-points incidence")
-    return start, entries
 
 
 def edge_points_composition(faces):
@@ -76,7 +62,7 @@ def edge_points_composition(faces):
     return torch.cat([edges, wing[lowest][:, None], wing[highest][:, None]], dim=1)
 
 
-class MeshEdgePoints(object):
+class MeshEdgePoints(_topology.VertexTable):
     """The edge-points topology of a batch of meshes over ``n_vertices`` vertices each.
 
     ``edge_points`` (Bt,Ecap,4) int64: rows ``[0, count[b])`` are ``[a, c, w0, w1]``, later rows ``-1``; ``counts``
@@ -87,146 +73,47 @@ class MeshEdgePoints(object):
     Building with ``from_faces`` / ``from_edge_points`` makes EXACTLY ONE device-to-host copy -- the counts and both
     flags together -- and nothing that uses the object afterwards synchronises with the host.  An index outside
     ``[0, n_vertices)`` raises IndexError and an edge with more than two incident half-edges ValueError, each naming
-    the batch element (the reference's ``build_gemm`` raises IndexError for the latter)."""
+    the batch element (the reference's ``build_gemm`` raises IndexError for the latter).  (The shared layer,
+    ``_mesh_topology``, keeps this.)"""
 
-    def __init__(self, edge_points, counts, counts_host, n_vertices, incidence=None):
-        self.edge_points = edge_points
-        self.counts = counts
-        self.counts_host = counts_host
-        self.n_vertices = int(n_vertices)
-        self._incidence = incidence
-
-    @property
-    def batch(self):
-        return self.edge_points.shape[0]
-
-    @property
-    def capacity(self):
-        return self.edge_points.shape[1]
-
-    def count(self, b):
-        """the number of edges of batch element ``b`` of the vertices (a Python int)"""
-        return self.counts_host[0 if self.batch == 1 else b]
+    COLS, NAME = 4, "edge_points"
+    edge_points = property(lambda self: self._rows)
 
     def table(self, b):
         """``(E_b,4)`` int64 view of the rows of batch element ``b``"""
-        return self.edge_points[0 if self.batch == 1 else b, :self.count(b)]
-
-    def incidence(self):
-        """``(start, entries)``; built here, without a host read, for an object made by ``_unchecked``"""
-        if self._incidence is None:
-            flags = torch.zeros(self.batch, dtype=torch.int32, device=self.edge_points.device)
-            self._incidence = _incidence_hip(self.edge_points, self.counts, self.n_vertices, flags)
-        return self._incidence
-
-    @classmethod
-    def _unchecked(cls, edge_points, n_vertices):
-        """int64 ``edge_points`` (Bt,E,4), every row an edge, nothing read back: the incidence is built on first use
-        and an out-of-range index is not reported (the step kernels give NaN for it)."""
-        bt, e = edge_points.shape[0], edge_points.shape[1]
-        counts = torch.full((bt,), e, dtype=torch.int32, device=edge_points.device)
-        return cls(edge_points, counts, (e,) * bt, n_vertices)
-
-    @staticmethod
-    def _raise_flagged(what, range_flags, manifold_flags=()):
-        for b, flag in enumerate(range_flags):
-            if flag:
-                raise IndexError("%s: batch element %d holds a vertex index outside [0, n_vertices)" % (what, b))
-        for b, flag in enumerate(manifold_flags):
-            if flag:
-                raise ValueError("%s: batch element %d has an edge with more than two incident half-edges (a "
-                                 "non-manifold edge or a duplicated face)" % (what, b))
+        return self._view(b)
 
     @classmethod
     def from_faces(cls, faces, n_vertices):
         """The table of the triangles ``faces`` (B,F,3) or (F,3), an integer tensor; the edge numbering is that of
         ``MeshEdges.from_faces(faces, n_vertices).edges``."""
         what = "MeshEdgePoints.from_faces"
-        if not isinstance(faces, torch.Tensor) or not _mesh_edges._is_index(faces):
-            raise TypeError("%s: faces must be an integer tensor, got %s"
-                            % (what, faces.dtype if isinstance(faces, torch.Tensor) else type(faces).__name__))
-        if faces.dim() == 2:
-            faces = faces.unsqueeze(0)
-        if faces.dim() != 3:
-            raise ValueError("%s: faces must have shape (B, F, 3), got %s" % (what, tuple(faces.shape)))
-        if faces.shape[-1] != 3:
-            raise NotImplementedError("%s: triangles only, got faces of %d corners" % (what, faces.shape[-1]))
+        faces = _topology.index_table(what, "faces", faces, "(B, F, 3)", None, triangles="")
         n_vertices = int(n_vertices)
-        if faces.shape[0] > 1 and faces.stride(0) == 0:
-            faces = faces[:1]
-        faces = (faces if faces.dtype == torch.int64 else faces.long()).contiguous()
         bt, f = faces.shape[0], faces.shape[1]
         if not faces.is_cuda:
-            bad = ((faces < 0) | (faces >= n_vertices)).reshape(bt, -1).any(1).tolist()
-            cls._raise_flagged(what, bad)
+            _topology.raise_flagged(what, _topology.out_of_range(faces, n_vertices))
             tables = []
             for b in range(bt):
                 try:
                     tables.append(edge_points_composition(faces[b]))
                 except ValueError:
-                    cls._raise_flagged(what, (), [0] * b + [1])
-            edge_points = faces.new_full((bt, 3 * f, 4), -1)
-            for b, rows in enumerate(tables):
-                edge_points[b, :rows.shape[0]] = rows
-            host = tuple(int(rows.shape[0]) for rows in tables)
-            return cls(edge_points, torch.tensor(host, dtype=torch.int32), host, n_vertices)
+                    _topology.raise_flagged(what, (), [0] * b + [1])
+            return cls._padded(tables, faces, 3 * f, n_vertices)
         status = torch.empty(3, bt, dtype=torch.int32, device=faces.device)   # counts, range flags, manifold flags
         status[2] = 0
         edges = _mesh_edges._unique_edges_hip(faces, n_vertices, status)
         edge_points = _edge_points_hip(faces, edges, status[0], status[2], n_vertices)
-        incidence = _incidence_hip(edge_points, status[0], n_vertices, status[1])
-        host = status.tolist()                       # the one copy: counts and both flags
-        cls._raise_flagged(what, host[1], host[2])
-        return cls(edge_points, status[0], tuple(host[0]), n_vertices, incidence)
+        return cls._read_back(what, edge_points, status, n_vertices)
 
     @classmethod
     def from_edge_points(cls, edge_points, n_vertices):
         """A user's table ``edge_points`` (E,4) -- shared by the batch -- or (B,E,4), an integer tensor, in any column
         order the reference's ``get_edge_points`` may give (the angle does not depend on it)."""
         what = "MeshEdgePoints.from_edge_points"
-        if not isinstance(edge_points, torch.Tensor) or not _mesh_edges._is_index(edge_points):
-            raise TypeError("%s: edge_points must be an integer tensor, got %s"
-                            % (what, edge_points.dtype if isinstance(edge_points, torch.Tensor)
-                               else type(edge_points).__name__))
-        if edge_points.dim() == 2:
-            edge_points = edge_points.unsqueeze(0)
-        if edge_points.dim() != 3 or edge_points.shape[-1] != 4:
-            raise ValueError("%s: edge_points must have shape (E, 4) or (B, E, 4), got %s"
-                             % (what, tuple(edge_points.shape)))
-        n_vertices = int(n_vertices)
-        if edge_points.shape[0] > 1 and edge_points.stride(0) == 0:
-            edge_points = edge_points[:1]
-        edge_points = (edge_points if edge_points.dtype == torch.int64 else edge_points.long()).contiguous()
-        bt, e = edge_points.shape[0], edge_points.shape[1]
-        if not edge_points.is_cuda:
-            bad = ((edge_points < 0) | (edge_points >= n_vertices)).reshape(bt, -1).any(1).tolist()
-            cls._raise_flagged(what, bad)
-            return cls(edge_points, torch.full((bt,), e, dtype=torch.int32), (e,) * bt, n_vertices)
-        status = torch.empty(2, bt, dtype=torch.int32, device=edge_points.device)
-        status[0] = e
-        status[1] = 0
-        incidence = _incidence_hip(edge_points, status[0], n_vertices, status[1])
-        host = status.tolist()                       # the one copy: counts and flags
-        cls._raise_flagged(what, host[1])
-        return cls(edge_points, status[0], tuple(host[0]), n_vertices, incidence)
-
-
-def _check(vertices, topo):
-    what = "mesh_dihedral_angle"
-    if not isinstance(topo, MeshEdgePoints):
-        raise TypeError("%s: topo must be a MeshEdgePoints, got %s" % (what, type(topo).__name__))
-    if vertices.dim() != 3 or vertices.shape[2] != 3:
-        raise ValueError("%s: vertices must have shape (B, N, 3), got %s" % (what, tuple(vertices.shape)))
-    if not vertices.is_floating_point():
-        raise RuntimeError("%s: vertices must be a floating tensor, got %s" % (what, vertices.dtype))
-    if vertices.shape[1] != topo.n_vertices:
-        raise ValueError("%s: the topology was built for %d vertices, got %d"
-                         % (what, topo.n_vertices, vertices.shape[1]))
-    if topo.batch not in (1, vertices.shape[0]):
-        raise ValueError("%s: a topology of %d batch elements does not serve %d vertex sets"
-                         % (what, topo.batch, vertices.shape[0]))
-    if topo.edge_points.device != vertices.device:
-        raise RuntimeError("%s: the topology is on %s, expected %s" % (what, topo.edge_points.device, vertices.device))
+        edge_points = _topology.index_table(what, "edge_points", edge_points, "(E, 4) or (B, E, 4)",
+                                            lambda cols: cols == 4)
+        return cls._from_rows(what, edge_points, int(n_vertices))
 
 
 def _unit(n):
@@ -244,7 +131,7 @@ def dihedral_composition(vertices, topo):
     ``pi - acos(d)``; padding rows 0; a row with an index outside [0, N) NaN.  An edge with a normal of length
     <= 1e-12 (a degenerate face) keeps the reference's value and contributes a zero gradient, where
     ``F.normalize``'s backward would give about 1e12."""
-    _check(vertices, topo)
+    _topology.check_vertices("mesh_dihedral_angle", vertices, topo, MeshEdgePoints, d3=True)
     b, n, _ = vertices.shape
     ecap = topo.capacity
     valid = torch.arange(ecap, device=vertices.device)[None, :] < topo.counts[:, None].long()      # (Bt,Ecap)
@@ -265,43 +152,9 @@ def dihedral_composition(vertices, topo):
     return torch.where(valid.expand(b, -1), angle, torch.zeros_like(angle))
 
 
-class MeshDihedralAngle(torch.autograd.Function):
-    """HIP forward and backward (CUDA fp32)."""
-
-    @staticmethod
-    def forward(ctx, vertices, topo):
-        dev = _lib.require_cuda(("vertices", vertices), ("edge_points", topo.edge_points))
-        vertices = vertices.contiguous()
-        b, n, _ = vertices.shape
-        ecap = topo.capacity
-        out = torch.empty(b, ecap, dtype=torch.float32, device=dev)
-        with _lib.on_device(dev) as stream:
-            _lib.check(_lib.lib().pp_mesh_dihedral_forward_f32(
-                _lib.ptr(vertices), _lib.ptr(topo.edge_points), _lib.ptr(topo.counts), _lib.ptr(out), b, n, ecap,
-                int(topo.batch == 1), stream), "mesh_dihedral_angle forward")
-        ctx.save_for_backward(vertices)
-        ctx.topo = topo
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        (vertices,) = ctx.saved_tensors
-        topo = ctx.topo
-        dev = vertices.device
-        b, n, _ = vertices.shape
-        grad_out = grad_out.contiguous()
-        grad = torch.empty_like(vertices)
-        with _lib.on_device(dev):
-            start, entries = topo.incidence()
-        with _lib.on_device(dev) as stream:
-            _lib.check(_lib.lib().pp_mesh_dihedral_backward_f32(
-                _lib.ptr(vertices), _lib.ptr(topo.edge_points), _lib.ptr(start), _lib.ptr(entries),
-                _lib.ptr(grad_out), _lib.ptr(grad), b, n, topo.capacity, int(topo.batch == 1), stream),
-                "mesh_dihedral_angle backward")
-        return grad, None
+MeshDihedralAngle = _topology.gather_function(
+    "MeshDihedralAngle", "HIP forward and backward (CUDA fp32).", "pp_mesh_dihedral_forward_f32",
+    "pp_mesh_dihedral_backward_f32", "mesh_dihedral_angle")
 
 
 def mesh_dihedral_angle(vertices, topo):
@@ -314,8 +167,9 @@ def mesh_dihedral_angle(vertices, topo):
     CUDA fp32: the HIP kernels (the backward gives the same bits on every run, so
     ``torch.use_deterministic_algorithms`` changes nothing); anything else: ``dihedral_composition``.  Nothing
     synchronises with the host."""
-    _check(vertices, topo)
+    _topology.check_vertices("mesh_dihedral_angle", vertices, topo, MeshEdgePoints, d3=True)
     if (vertices.is_cuda and vertices.dtype == torch.float32
-            and vertices.shape[0] * max(topo.capacity, vertices.shape[1]) <= _LIMIT and 4 * topo.capacity <= _LIMIT):
+            and vertices.shape[0] * max(topo.capacity, vertices.shape[1]) <= _topology.LIMIT
+            and 4 * topo.capacity <= _topology.LIMIT):
         return MeshDihedralAngle.apply(vertices, topo)
     return dihedral_composition(vertices, topo)

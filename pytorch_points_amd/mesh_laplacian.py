@@ -16,12 +16,14 @@ once (one device-to-host copy) and kept; an apply is one launch, forward or back
 host.  CUDA fp32 with D = 3 runs the HIP kernels of csrc/mesh_edges.hip (``pp_mesh_corner_incidence``,
 ``pp_mesh_cotangent_f32``, ``pp_mesh_laplacian_apply_f32``): no floating-point atomics, the same bits on every run, one
 form only.  CPU tensors, other dtypes and D go through the ``*_composition`` twins, the same contracts written with
-``index_add_`` over the corner list.  DESIGN.md "Mesh Laplacians" states the contract.
+``index_add_`` over the corner list.  ``MeshCorners`` is an object of its own (no counts); its input normalising,
+range check, errors and the applies' argument checks are ``_mesh_topology``'s.  DESIGN.md "Mesh Laplacians" states the
+contract.
 """
 import torch
 
 from . import _lib
-from .mesh_edges import _LIMIT, _fits, _is_index, _workspace
+from . import _mesh_topology as _topology
 
 
 class MeshCorners(object):
@@ -72,23 +74,13 @@ class MeshCorners(object):
     def from_faces(cls, faces, n_vertices):
         """``faces`` (F,L), (1,F,L) or (B,F,L), an integer tensor with L >= 3.  A face with a repeated vertex keeps
         all its corners, as the reference's sparse sum does."""
-        if not isinstance(faces, torch.Tensor) or not _is_index(faces):
-            raise TypeError("MeshCorners.from_faces: faces must be an integer tensor, got %s"
-                            % (faces.dtype if isinstance(faces, torch.Tensor) else type(faces).__name__))
-        if faces.dim() == 2:
-            faces = faces.unsqueeze(0)
-        if faces.dim() != 3 or faces.shape[-1] < 3:
-            raise ValueError("MeshCorners.from_faces: faces must have shape (B, F, L) with L >= 3, got %s"
-                             % (tuple(faces.shape),))
+        what = "MeshCorners.from_faces"
+        faces = _topology.index_table(what, "faces", faces, "(B, F, L) with L >= 3", lambda cols: cols >= 3)
         n_vertices = int(n_vertices)
-        if faces.shape[0] > 1 and faces.stride(0) == 0:
-            faces = faces[:1]
-        faces = (faces if faces.dtype == torch.int64 else faces.long()).contiguous()
         bt, f, deg = faces.shape
-        _fits("corner incidence", bt, n_vertices, deg * f)
+        _topology.fits("corner incidence", bt, n_vertices, deg * f)
         if not faces.is_cuda:
-            bad = ((faces < 0) | (faces >= n_vertices)).reshape(bt, -1).any(1).tolist()
-            cls._raise_flagged(bad)
+            _topology.raise_flagged(what, _topology.out_of_range(faces, n_vertices))
             keys = faces.reshape(bt, deg * f)
             codes = torch.argsort(keys, dim=1, stable=True)              # position L*f + c of every corner, by vertex
             count = torch.zeros(bt, n_vertices + 1, dtype=torch.int64)
@@ -102,36 +94,12 @@ class MeshCorners(object):
         nbr = torch.empty(bt, deg * f, 2, dtype=torch.int32, device=dev)
         flags = torch.empty(bt, dtype=torch.int32, device=dev)
         with _lib.on_device(dev) as stream:
-            wsp, nbytes, ws = _workspace(dev, bt, n_vertices, deg * f)
+            wsp, nbytes, ws = _topology.workspace(dev, bt, n_vertices, deg * f)
             _lib.check(_lib.lib().pp_mesh_corner_incidence(
                 _lib.ptr(faces), _lib.ptr(start), _lib.ptr(codes), _lib.ptr(nbr), _lib.ptr(flags), bt, f, deg,
                 n_vertices, wsp, nbytes, stream), "mesh corner incidence")
-        cls._raise_flagged(flags.tolist())                               # the one copy
+        _topology.raise_flagged(what, flags.tolist())                    # the one copy
         return cls(faces, start, codes, nbr, n_vertices)
-
-    @staticmethod
-    def _raise_flagged(flags):
-        for b, flag in enumerate(flags):
-            if flag:
-                raise IndexError("MeshCorners.from_faces: batch element %d holds a vertex index outside "
-                                 "[0, n_vertices)" % b)
-
-
-def _check(what, vertices, corners):
-    if not isinstance(corners, MeshCorners):
-        raise TypeError("%s: corners must be a MeshCorners, got %s" % (what, type(corners).__name__))
-    if vertices.dim() != 3:
-        raise ValueError("%s: vertices must have shape (B, N, D), got %s" % (what, tuple(vertices.shape)))
-    if not vertices.is_floating_point():
-        raise RuntimeError("%s: vertices must be a floating tensor, got %s" % (what, vertices.dtype))
-    if vertices.shape[1] != corners.n_vertices:
-        raise ValueError("%s: the topology was built for %d vertices, got %d"
-                         % (what, corners.n_vertices, vertices.shape[1]))
-    if corners.batch not in (1, vertices.shape[0]):
-        raise ValueError("%s: a topology of %d batch elements does not serve %d vertex sets"
-                         % (what, corners.batch, vertices.shape[0]))
-    if corners.device != vertices.device:
-        raise RuntimeError("%s: the topology is on %s, expected %s" % (what, corners.device, vertices.device))
 
 
 def _check_weights(what, vertices, corners, weights):
@@ -155,7 +123,7 @@ def _corner_rows(vertices, corners):
 def uniform_laplacian_composition(vertices, corners):
     """``mesh_uniform_laplacian`` as torch operations, for any device, floating dtype and D: one ``index_add_`` over
     the corner list, then the division by ``Lii + 1e-12``."""
-    _check("mesh_uniform_laplacian", vertices, corners)
+    _topology.check_vertices("mesh_uniform_laplacian", vertices, corners, MeshCorners, "corners", "faces")
     b, n, d = vertices.shape
     flat = vertices.reshape(b * n, d)
     i, nxt, prv = _corner_rows(vertices, corners)
@@ -168,7 +136,7 @@ def uniform_laplacian_composition(vertices, corners):
 def cot_laplacian_composition(vertices, corners, weights):
     """``mesh_cot_laplacian`` as torch operations, for any device, floating dtype and D (differentiable in the
     weights too, which the kernels are not)."""
-    _check("mesh_cot_laplacian", vertices, corners)
+    _topology.check_vertices("mesh_cot_laplacian", vertices, corners, MeshCorners, "corners", "faces")
     _check_weights("mesh_cot_laplacian", vertices, corners, weights)
     b, n, d = vertices.shape
     flat = vertices.reshape(b * n, d)
@@ -213,13 +181,13 @@ def cotangent(vertices, faces):
     ``cotangent_composition``."""
     if (vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 3 and vertices.shape[2] == 3
             and not (vertices.requires_grad and torch.is_grad_enabled()) and isinstance(faces, torch.Tensor)
-            and _is_index(faces) and faces.dim() in (2, 3) and faces.shape[-1] == 3):
+            and _topology.is_index(faces) and faces.dim() in (2, 3) and faces.shape[-1] == 3):
         if faces.dim() == 2:
             faces = faces.unsqueeze(0)
         b, n, f = vertices.shape[0], vertices.shape[1], faces.shape[1]
         if faces.shape[0] > 1 and faces.stride(0) == 0:
             faces = faces[:1]
-        if faces.shape[0] in (1, b) and b * max(f, n) <= _LIMIT:
+        if faces.shape[0] in (1, b) and b * max(f, n) <= _topology.LIMIT:
             dev = vertices.device
             faces = faces.to(device=dev, dtype=torch.int64).contiguous()
             vertices = vertices.detach().contiguous()
@@ -284,7 +252,7 @@ class MeshCotLaplacian(torch.autograd.Function):
 
 def _hip_serves(vertices):
     return (vertices.is_cuda and vertices.dtype == torch.float32 and vertices.shape[2] == 3
-            and vertices.shape[0] * vertices.shape[1] <= _LIMIT)
+            and vertices.shape[0] * vertices.shape[1] <= _topology.LIMIT)
 
 
 def mesh_uniform_laplacian(vertices, corners):
@@ -297,7 +265,7 @@ def mesh_uniform_laplacian(vertices, corners):
     CUDA fp32 with D = 3: the HIP gather, forward and backward, bit for bit the sequential fp32 loop over the sorted
     slices on every run (``torch.use_deterministic_algorithms`` selects nothing); anything else:
     ``uniform_laplacian_composition``.  Nothing synchronises with the host."""
-    _check("mesh_uniform_laplacian", vertices, corners)
+    _topology.check_vertices("mesh_uniform_laplacian", vertices, corners, MeshCorners, "corners", "faces")
     if _hip_serves(vertices):
         return MeshUniformLaplacian.apply(vertices, corners)
     return uniform_laplacian_composition(vertices, corners)
@@ -312,7 +280,7 @@ def mesh_cot_laplacian(vertices, corners, weights):
 
     CUDA fp32 with D = 3 and weights that need no gradient: the HIP gather, forward and backward; anything else:
     ``cot_laplacian_composition``.  Nothing synchronises with the host."""
-    _check("mesh_cot_laplacian", vertices, corners)
+    _topology.check_vertices("mesh_cot_laplacian", vertices, corners, MeshCorners, "corners", "faces")
     _check_weights("mesh_cot_laplacian", vertices, corners, weights)
     if (_hip_serves(vertices) and weights.dtype == torch.float32
             and not (weights.requires_grad and torch.is_grad_enabled())):

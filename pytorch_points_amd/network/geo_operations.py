@@ -15,6 +15,7 @@ import torch
 
 from .. import green as _green
 from .. import knn_edges as _knn_edges
+from .. import _mesh_topology
 from .. import mesh_dihedral as _mesh_dihedral
 from .. import mesh_edges as _mesh_edges
 from .. import mesh_laplacian as _mesh_laplacian
@@ -173,7 +174,7 @@ def edge_vertex_indices(F):
         return np.unique(pairs.reshape([-1, 2]), axis=0)
     if F.dim() != 2 or F.shape[1] != 3:
         raise NotImplementedError("edge_vertex_indices: F must have shape (F, 3) (triangles), got %s" % (tuple(F.shape),))
-    if not _mesh_edges._is_index(F):
+    if not _mesh_topology.is_index(F):
         raise TypeError("edge_vertex_indices: F must be an integer tensor, got %s" % F.dtype)
     if not F.is_cuda or F.shape[0] == 0:
         return _mesh_edges.unique_edges_composition(F)
@@ -196,7 +197,7 @@ def get_edge_lengths(vertices, edge_points):
         raise ValueError("get_edge_lengths: vertices (N, D) and edge_points (E, >= 2), got %s and %s"
                          % (tuple(vertices.shape), tuple(edge_points.shape)))
     if vertices.is_cuda and vertices.dtype == torch.float32 and vertices.shape[1] == 3 and edge_points.is_cuda:
-        if not _mesh_edges._is_index(edge_points):
+        if not _mesh_topology.is_index(edge_points):
             raise TypeError("get_edge_lengths: edge_points must be an integer tensor, got %s" % edge_points.dtype)
         edges = edge_points[:, :2].long().contiguous().unsqueeze(0)
         topo = _mesh_edges.MeshEdges._unchecked(edges, vertices.shape[0])
@@ -229,7 +230,7 @@ def get_edge_points(faces_or_mesh, n_vertices=None):
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise NotImplementedError("get_edge_points: faces must have shape (F, 3) (triangles), got %s"
                                   % (tuple(faces.shape),))
-    if not _mesh_edges._is_index(faces):
+    if not _mesh_topology.is_index(faces):
         raise TypeError("get_edge_points: faces must be integers, got %s" % faces.dtype)
     if faces.shape[0] == 0:
         table = faces.new_empty((0, 4), dtype=torch.int64)
@@ -261,7 +262,7 @@ def dihedral_angle(vertices, edge_points):
     if vertices.dim() != 2 or vertices.shape[1] != 3 or edge_points.dim() != 2 or edge_points.shape[1] != 4:
         raise ValueError("dihedral_angle: vertices (N, 3) and edge_points (E, 4), got %s and %s"
                          % (tuple(vertices.shape), tuple(edge_points.shape)))
-    if not _mesh_edges._is_index(edge_points):
+    if not _mesh_topology.is_index(edge_points):
         raise TypeError("dihedral_angle: edge_points must be an integer tensor, got %s" % edge_points.dtype)
     if edge_points.is_cuda:
         topo = _mesh_dihedral.MeshEdgePoints._unchecked(edge_points.long().contiguous().unsqueeze(0), vertices.shape[0])

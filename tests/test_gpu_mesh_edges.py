@@ -3,6 +3,7 @@ losses over them: the unique edges bit for bit against numpy, the out-of-range c
 knn_edge_lengths, the backward bit for bit against a sequential numpy loop, the incidence lists, the losses against
 the fp64 CPU composition, graph capture and a side stream, and the reference-API utilities on CUDA tensors."""
 import contextlib
+import ctypes
 import functools
 import os
 
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from pytorch_points_amd import knn_edges, mesh_edges, synthetic
+from pytorch_points_amd import _lib, knn_edges, mesh_edges, synthetic
 from pytorch_points_amd.network import geo_operations, model_loss
 from test_mesh_edges_host import (REDUCTIONS, fan_mesh, grid_mesh, jittered_grid, np_unique_edges, soup_mesh,
                                   tetrahedron)
@@ -239,6 +240,31 @@ def test_incidence_of_a_shuffled_duplicated_edge_list(cuda):
     for v in range(n):
         got = inc_entries[0, inc_start[0, v]:inc_start[0, v + 1]]
         assert np.array_equal(got, np.flatnonzero(flat == v))       # sorted, and the same multiset (codes are distinct)
+
+
+@pytest.mark.parametrize("counts", [(0, 4), (2, 3)])
+def test_incidence_of_counted_rows(cuda, counts):
+    """pp_mesh_edge_incidence itself, Ecap = 4: only the rows e < counts[b] are listed"""
+    n, ecap = 5, 4
+    edges = np.random.default_rng(7).integers(0, n, size=(2, ecap, 2)).astype(np.int64)
+    te, tc = dev_t(edges), dev_t(np.asarray(counts, np.int32))
+    inc_start = torch.full((2, n + 1), -7, dtype=torch.int32, device="cuda")
+    inc_entries = torch.full((2, 2 * ecap), -7, dtype=torch.int32, device="cuda")
+    flags = torch.zeros(2, dtype=torch.int32, device="cuda")
+    nbytes = int(_lib.lib().pp_mesh_edges_workspace_bytes(2, n, 2 * ecap))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    with _lib.on_device(te.device) as stream:
+        _lib.check(_lib.lib().pp_mesh_edge_incidence(_lib.ptr(te), _lib.ptr(tc), _lib.ptr(inc_start),
+                                                     _lib.ptr(inc_entries), _lib.ptr(flags), 2, ecap, n, _lib.ptr(ws),
+                                                     ctypes.c_size_t(nbytes), stream), "edge incidence")
+    inc_start, inc_entries = inc_start.cpu().numpy(), inc_entries.cpu().numpy()
+    assert not flags.cpu().numpy().any()
+    for b in range(2):
+        flat = edges[b, :counts[b]].reshape(-1)
+        assert inc_start[b, 0] == 0 and inc_start[b, n] == 2 * counts[b]
+        for v in range(n):
+            got = inc_entries[b, inc_start[b, v]:inc_start[b, v + 1]]
+            assert np.array_equal(got, np.flatnonzero(flat == v))
 
 
 # ------------------------------------------------------------------------------------------------- 6. losses

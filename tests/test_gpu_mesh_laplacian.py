@@ -4,13 +4,14 @@ numpy, the out-of-range contract, the cotangent kernel against the fp64 composit
 bit for bit against a sequential numpy fp32 loop over the sorted slices, the operators and losses against the fp64 CPU
 compositions, graph capture and a side stream."""
 import contextlib
+import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-from pytorch_points_amd import mesh_laplacian, synthetic
+from pytorch_points_amd import _lib, mesh_laplacian, synthetic
 from pytorch_points_amd.network import geo_operations, model_loss
 from test_mesh_edges_host import fan_mesh, grid_mesh, jittered_grid, soup_mesh
 from test_mesh_laplacian_host import quad_grid, with_isolated_vertex
@@ -104,6 +105,45 @@ def test_out_of_range_index_raises_and_the_stream_goes_on(cuda):
             assert_corners(corners, b, faces[b], 99)
         with pytest.raises(IndexError, match="batch element 0"):
             geo_operations.UniformLaplacian()(dev_t(synthetic.unit_sphere(1, 2, 99)), dev_t(bad[::-1]))
+
+
+def corner_lists(faces, n):
+    """pp_mesh_corner_incidence itself on ``faces`` (Bt,F,L) over ``n`` vertices, whatever the flags say: (start, codes,
+    nbr, flags) as numpy; the outputs are handed over filled with -7"""
+    tf = dev_t(faces)
+    bt, f, deg = faces.shape
+    out = [torch.full(shape, -7, dtype=torch.int32, device="cuda")
+           for shape in ((bt, n + 1), (bt, deg * f), (bt, deg * f, 2), (bt,))]
+    nbytes = int(_lib.lib().pp_mesh_edges_workspace_bytes(bt, n, deg * f))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    with _lib.on_device(tf.device) as stream:
+        _lib.check(_lib.lib().pp_mesh_corner_incidence(_lib.ptr(tf), *(_lib.ptr(t) for t in out), bt, f, deg, n,
+                                                       _lib.ptr(ws), ctypes.c_size_t(nbytes), stream), "corner lists")
+    return tuple(t.cpu().numpy() for t in out)
+
+
+@pytest.mark.parametrize("deg", [3, 4])
+def test_corner_lists_of_the_smallest_batch(cuda, deg):
+    """Bt=2, N=5, F=3: the lists byte for byte; then an index N in element 1 only: its flag alone, element 0 intact"""
+    faces = np.random.default_rng(60 + deg).integers(0, 5, size=(2, 3, deg)).astype(np.int64)
+    start, codes, nbr, flags = corner_lists(faces, 5)
+    assert not flags.any()
+    for b in range(2):
+        for got, want in zip((start[b], codes[b], nbr[b]), np_corners(faces[b], 5)):
+            assert got.tobytes() == want.tobytes()
+    bad = faces.copy()
+    bad[1, 1, 1] = 5
+    start, codes, nbr, flags = corner_lists(bad, 5)
+    assert flags[0] == 0 and flags[1] != 0
+    for got, want in zip((start[0], codes[0], nbr[0]), np_corners(faces[0], 5)):
+        assert got.tobytes() == want.tobytes()
+
+
+def test_corner_lists_without_faces_and_without_vertices(cuda):
+    start, _, _, flags = corner_lists(np.zeros((2, 0, 3), np.int64), 5)
+    assert start.shape == (2, 6) and not start.any() and not flags.any()
+    start, _, _, flags = corner_lists(np.zeros((2, 1, 3), np.int64), 0)          # every corner is out of range
+    assert start.shape == (2, 1) and not start.any() and flags.all()
 
 
 # ----------------------------------------------------------------------------------------------- 2. cotangent
