@@ -578,6 +578,41 @@ int pp_mesh_dihedral_backward_f32(const float* vertices, const long long* edge_p
                                   const unsigned* entries, const float* grad_out, float* grad_vertices, int B, int N,
                                   int Ecap, int shared_topology, void* stream);
 
+/* ---- mesh normals ---------------------------------------------------------------------------
+ * The unit normals and areas of a triangle mesh's faces (the reference's compute_face_normals_and_areas,
+ * geo_operations.py:529-559) and the unit normals of its vertices; contract in DESIGN.md "Mesh normals".  fp32 vertices
+ * (B,N,3); faces (Bt,F,3) int64 and start (Bt,N+1), codes (Bt,3F), nbr (Bt,3F,2) as pp_mesh_corner_incidence made them
+ * for L == 3.  shared_topology != 0: they have one batch element, read by every b; gradients and outputs are always per
+ * batch element.  Every entry returns PP_EINVAL where B*N, B*F or 3F exceeds 2^31 - 1 or a size is negative, before any
+ * launch, and PP_OK without a launch where B, N or F is 0.
+ * pp_mesh_face_normals_forward_f32: with p_k = vertices[b, faces[f,k]], c = (p1-p0) x (p2-p1), the products a*b - c*d
+ *   with explicit fused multiply-adds (Kahan's difference of products); len = sqrtf((cx*cx + cy*cy) + cz*cz);
+ *   areas (B,F) = len * 0.5f; normals (B,F,3) = c / max(len, 1e-12f).
+ * pp_mesh_face_normals_backward_f32: grad_vertices (B,N,3), overwritten: every vertex walks its slice in slot order;
+ *   the slot 3f + c gives p0, p1, p2 from (the vertex, next, prev) and c, the forward chain is evaluated again, with
+ *   u = c / len, G = (g_n - u (u.g_n)) / len + (g_a * 0.5f) u the slot adds (v_next - v_prev) x G; plain fp32 sums from
+ *   +0.  A face with len <= 1e-12f adds 0.  grad_normals (B,F,3) or grad_areas (B,F) may be NULL (taken as 0).
+ * pp_mesh_vertex_normals_forward_f32: out (B,N,3): S = sum over the vertex's slots in order of w(c), c = (v_next - v_i)
+ *   x (v_prev - v_i); weighting 0 ("area") w(c) = c, 1 ("uniform") w(c) = c / max(|c|, 1e-12f);
+ *   out = S / max(|S|, 1e-12f); a vertex without corners gives +0.  Anything else for weighting is PP_EINVAL.
+ * pp_mesh_vertex_normals_backward_f32: grad_vertices (B,N,3), overwritten, in two launches: (a) per vertex S again and
+ *   h = (g - n (n.g)) / |S|, n = S / |S|, 0 where |S| <= 1e-12f, into scratch (B,N,3) fp32, the caller's, not
+ *   grad_vertices; (b) per vertex over its slots H = (h_i + h_next) + h_prev, for weighting 1 H <- (H - u (u.H)) / |c|
+ *   with u = c / |c| (0 where |c| <= 1e-12f), and the slot adds (v_next - v_prev) x H.
+ * No floating-point atomics: every word is written once, identical on every run.  A neighbour outside [0,N) (the build
+ * stores -1), a face index outside [0,N) and a slot code >= 3F are only compared, never used as an address: the lane's
+ * results are NaN. */
+int pp_mesh_face_normals_forward_f32(const float* vertices, const long long* faces, float* normals, float* areas, int B,
+                                     int N, int F, int shared_topology, void* stream);
+int pp_mesh_face_normals_backward_f32(const float* vertices, const int* start, const int* nbr, const unsigned* codes,
+                                      const float* grad_normals, const float* grad_areas, float* grad_vertices, int B,
+                                      int N, int F, int shared_topology, void* stream);
+int pp_mesh_vertex_normals_forward_f32(const float* vertices, const int* start, const int* nbr, float* out, int B,
+                                       int N, int F, int weighting, int shared_topology, void* stream);
+int pp_mesh_vertex_normals_backward_f32(const float* vertices, const int* start, const int* nbr, const float* grad_out,
+                                        float* scratch, float* grad_vertices, int B, int N, int F, int weighting,
+                                        int shared_topology, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -27,7 +27,7 @@
 //
 // An index outside [0, n_vertices) is never used as an address: the builds compare it and leave out what it belongs
 // to, the forward writes NaN for such an edge and the backward adds NaN for it.
-#include "mesh_common.h"   // pp::mesh_half_edge, pp::mesh_build_ok; pp::blocks, pp::quiet_nan
+#include "mesh_common.h"   // pp::mesh_half_edge, pp::mesh_build_ok, the three-vectors; pp::blocks, pp::quiet_nan
 
 namespace {
 
@@ -115,26 +115,11 @@ __global__ __launch_bounds__(kMdThreads) void md_decode_kernel(const long long* 
 }
 
 // ---- the chain ----------------------------------------------------------------------------------------------------
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 md_load(const float* __restrict__ vb, long long i) {
-  return {vb[i * 3], vb[i * 3 + 1], vb[i * 3 + 2]};
-}
-__device__ __forceinline__ V3 md_sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-// a*b - c*d within 1.5 ulp (Kahan): the rounding error of c*d is recovered by one fma and added back
-__device__ __forceinline__ float md_dop(float a, float b, float c, float d) {
-  const float w = c * d;
-  const float e = __builtin_fmaf(-c, d, w);
-  const float f = __builtin_fmaf(a, b, -w);
-  return f + e;
-}
-__device__ __forceinline__ V3 md_cross(V3 a, V3 b) {
-  return {md_dop(a.y, b.z, a.z, b.y), md_dop(a.z, b.x, a.x, b.z), md_dop(a.x, b.y, a.y, b.x)};
-}
-__device__ __forceinline__ float md_dot(V3 a, V3 b) {
-  return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x));   // symmetric in a and b
-}
+using pp::V3;   // mesh_common.h: md_load, md_sub, md_dop (Kahan's difference of products), md_cross, md_dot
+using pp::md_cross;
+using pp::md_dot;
+using pp::md_load;
+using pp::md_sub;
 
 // a row in canonical order (ends ascending, wings ascending) and what became of the caller's slots
 struct MdRow {

@@ -6,7 +6,9 @@ face normals those need, compute_face_normals_and_areas (:529-559), the point-cl
 pointUniformLaplacian (:128-152), the mesh Laplacians UniformLaplacian, CotLaplacian and cotangent (:155-346), and
 the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600), and the face-to-face angles get_normals
 (:603-619, without its stray check_values line) and dihedral_angle (:775-789) with the (E,4) table they work on,
-get_edge_points (utils/geometry_utils.py:242-341: build_gemm, get_edge_points, get_side_points).
+get_edge_points (utils/geometry_utils.py:242-341: build_gemm, get_edge_points, get_side_points), and the mesh normals
+mesh_face_normals / mesh_vertex_normals (the reference has no vertex normals) with normalize_to_same_area
+(utils/geometry_utils.py:15-25).
 Only green_coordinates_2D, an empty stub in the reference, stays out."""
 import collections
 
@@ -19,6 +21,7 @@ from .. import _mesh_topology
 from .. import mesh_dihedral as _mesh_dihedral
 from .. import mesh_edges as _mesh_edges
 from .. import mesh_laplacian as _mesh_laplacian
+from .. import mesh_normals as _mesh_normals
 from .. import mvc as _mvc
 from .. import mvc2d as _mvc2d
 from .. import ops
@@ -269,6 +272,46 @@ def dihedral_angle(vertices, edge_points):
     else:
         topo = _mesh_dihedral.MeshEdgePoints.from_edge_points(edge_points, vertices.shape[0])
     return _mesh_dihedral.mesh_dihedral_angle(vertices.unsqueeze(0), topo)[0]
+
+
+# ----------------------------------------------------------------------------------------------- mesh normals
+def _corners_of(what, vertices, faces_or_corners):
+    """a ``MeshCorners`` as it is; a faces tensor (F,3) / (B,F,3) builds one for this call (one host read)"""
+    if isinstance(faces_or_corners, _mesh_laplacian.MeshCorners):
+        return faces_or_corners
+    if not isinstance(faces_or_corners, torch.Tensor):
+        raise TypeError("%s: faces_or_corners must be an integer tensor or a MeshCorners, got %s"
+                        % (what, type(faces_or_corners).__name__))
+    if vertices.dim() != 3:
+        raise ValueError("%s: vertices must have shape (B, N, 3), got %s" % (what, tuple(vertices.shape)))
+    return _mesh_laplacian.MeshCorners.from_faces(faces_or_corners.to(vertices.device), vertices.shape[1])
+
+
+def mesh_face_normals(vertices, faces_or_corners):
+    """``(normals (B,F,3), areas (B,F))`` of a triangle mesh: ``compute_face_normals_and_areas``' values through
+    ``pytorch_points_amd.mesh_normals.mesh_face_normals`` -- on CUDA fp32 one HIP launch forward and a gather backward
+    with no floating-point atomics; a face without area passes no gradient (there: NaN).  ``faces_or_corners``: the
+    faces (F,3) or (B,F,3), whose corner lists are then built for this call, or a kept ``MeshCorners``."""
+    corners = _corners_of("mesh_face_normals", vertices, faces_or_corners)
+    return _mesh_normals.mesh_face_normals(vertices, corners)
+
+
+def mesh_vertex_normals(vertices, faces_or_corners, weighting="area"):
+    """Unit vertex normals ``(B,N,3)`` of a triangle mesh (the reference has none): the normalised sum over a
+    vertex's corners of the face's cross product (``weighting="area"``) or unit normal (``"uniform"``); ``+0`` for a
+    vertex no face uses (``pytorch_points_amd.mesh_normals.mesh_vertex_normals``).  ``faces_or_corners`` as in
+    ``mesh_face_normals``."""
+    corners = _corners_of("mesh_vertex_normals", vertices, faces_or_corners)
+    return _mesh_normals.mesh_vertex_normals(vertices, corners, weighting)
+
+
+def normalize_to_same_area(v_ref, f_ref, v, f):
+    """``v`` (B,N,3) scaled so that the mesh ``(v, f)`` has the surface area of ``(v_ref, f_ref)``:
+    ``v * sqrt(sum(A_ref) / sum(A))`` per batch element (reference utils/geometry_utils.py:15-25).  Differentiable in
+    both vertex sets; either face argument is a faces tensor or a kept ``MeshCorners``."""
+    area_ref = mesh_face_normals(v_ref, f_ref)[1].sum(dim=-1)
+    area = mesh_face_normals(v, f)[1].sum(dim=-1)
+    return v * torch.sqrt(area_ref / area).unsqueeze(-1).unsqueeze(-1)
 
 
 # ------------------------------------------------------------------------------------------- mesh Laplacians

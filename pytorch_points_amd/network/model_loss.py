@@ -4,7 +4,7 @@ point-cloud regularisers PointLaplacianLoss, PointEdgeLengthLoss, PointStretchLo
 SimplePointRepulsionLoss (:73-163, :310-398) over pytorch_points_amd.knn_edges, and the mesh edge losses
 MeshEdgeLengthLoss, MeshStretchLoss and SimpleMeshRepulsionLoss (:166-308) over pytorch_points_amd.mesh_edges, and
 the mesh Laplacian losses UniformLaplacianSmoothnessLoss and MeshLaplacianLoss (:8-71) over
-pytorch_points_amd.mesh_laplacian.
+pytorch_points_amd.mesh_laplacian, and MeshNormalLoss over pytorch_points_amd.mesh_normals.
 
 ``nndistance`` / ``labeled_nndistance`` are the C++ autograd nodes of csrc/torch_bridge.cpp (the reference's
 host side is a C++ extension too): at config 2 the step's kernels take less time than Python needs to issue
@@ -17,6 +17,8 @@ from .. import _lib
 from .. import knn_edges as _knn_edges
 from .. import mesh_dihedral as _mesh_dihedral
 from .. import mesh_edges as _mesh_edges
+from .. import mesh_laplacian as _mesh_laplacian
+from .. import mesh_normals as _mesh_normals
 from .. import ops
 from .._ext import losses
 
@@ -447,6 +449,35 @@ class MeshDihedralAngleLoss(torch.nn.Module):
             assert(self.threshold is not None), "threshold is required without vert2"
             diff = torch.relu(self.threshold - angle1)
         return _reduce_edges(diff * diff, topo, self.reduction)
+
+
+class MeshNormalLoss(torch.nn.Module):
+    """``metric`` between the normals of two meshes of one connectivity, ``vert1`` and ``vert2`` (B,N,3) over ``face``
+    (B,F,3) or a shared (F,3): the unit vertex normals (B,N,3) of ``pytorch_points_amd.mesh_normals
+    .mesh_vertex_normals`` with ``weighting`` "area" or "uniform", or with ``use_face`` the unit face normals (B,F,3)
+    of ``mesh_face_normals``.  The reference has no such module; the signature follows its mesh losses.  ``metric`` is
+    any callable of two tensors (``torch.nn.MSELoss()``, a cosine loss).  ``self.E`` is the ``MeshCorners`` of the last
+    build; it is kept, and never checked against later faces, while ``consistent_topology`` is set."""
+
+    def __init__(self, metric, use_face=False, weighting="area", consistent_topology=False):
+        super().__init__()
+        self.metric = metric
+        self.use_face = use_face
+        self.weighting = weighting
+        self.consistent_topology = consistent_topology
+        self.E = None
+
+    def _normals(self, vert):
+        if self.use_face:
+            return _mesh_normals.mesh_face_normals(vert, self.E)[0]
+        return _mesh_normals.mesh_vertex_normals(vert, self.E, self.weighting)
+
+    def forward(self, vert1, vert2, face=None):
+        assert(vert1.shape == vert2.shape)
+        if (not self.consistent_topology) or (self.E is None):
+            assert(face is not None), "Face is required"
+            self.E = _mesh_laplacian.MeshCorners.from_faces(face.to(vert1.device), vert1.shape[1])
+        return self.metric(self._normals(vert1), self._normals(vert2))
 
 
 # ---------------------------------------------------------------------------------------- mesh Laplacian losses
