@@ -417,6 +417,35 @@ int pp_mvc2d_backward_f64(const double* points, const double* polygon, const dou
                           double* grad_polygon, int B, int N, int M, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- Green coordinates, 2-D ---------------------------------------------------------------
+ * network.geo_operations.green_coordinates_2D(query, vertices, faces, edge_normals), which the reference declares and
+ * leaves empty (geo_operations.py:622); contract in DESIGN.md "Green coordinates, 2-D".  query (B,P,2), vertices
+ * (B,N,2), faces int64 (B,F,2), row j the directed edge (v1, v2), read at faces + b * faces_batch_stride (elements;
+ * 0 = one edge list for every batch element); edge_normals (B,F,2), nullable, only orients: an edge whose own normal
+ * (a_y, -a_x), a = v2 - v1, points against its row is taken reversed.  Forward -> phi (B,P,N) vertex coordinates (not
+ * renormalised), psi (B,P,F) edge coordinates, exterior (B,P) bytes 0 / 1 (the fp64 row sum of phi < 0.5), codes (B,P)
+ * int32 (8: an out-of-range index in the batch element; 1: a non-finite pair; the rows are NaN and exterior 0).
+ * Backward: grad_phi (B,P,N) and grad_psi (B,P,F), either nullable -> grad_query (B,P,2), grad_vertices (B,N,2), with a
+ * workspace of pp_gc2d_workspace_bytes(B,P,F,sizeof element) bytes (0 for an element size that is not served).  A size
+ * of zero is served; a negative size returns PP_EINVAL before any pointer is looked at.  Every pair is evaluated in
+ * fp64 for either data type.  No floating-point atomics: every output is reproducible bit for bit, and a query's row
+ * does not depend on the other queries. */
+size_t pp_gc2d_workspace_bytes(int B, int P, int F, int elem_bytes);
+int pp_gc2d_forward_f32(const float* query, const float* vertices, const long long* faces,
+                        long long faces_batch_stride, const float* edge_normals, float* phi, float* psi,
+                        unsigned char* exterior, int* codes, int B, int P, int N, int F, void* stream);
+int pp_gc2d_forward_f64(const double* query, const double* vertices, const long long* faces,
+                        long long faces_batch_stride, const double* edge_normals, double* phi, double* psi,
+                        unsigned char* exterior, int* codes, int B, int P, int N, int F, void* stream);
+int pp_gc2d_backward_f32(const float* query, const float* vertices, const long long* faces,
+                         long long faces_batch_stride, const float* edge_normals, const int* codes,
+                         const float* grad_phi, const float* grad_psi, float* grad_query, float* grad_vertices, int B,
+                         int P, int N, int F, void* workspace, size_t workspace_bytes, void* stream);
+int pp_gc2d_backward_f64(const double* query, const double* vertices, const long long* faces,
+                         long long faces_batch_stride, const double* edge_normals, const int* codes,
+                         const double* grad_phi, const double* grad_psi, double* grad_query, double* grad_vertices,
+                         int B, int P, int N, int F, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- k-NN edge operators -------------------------------------------------------------------
  * The (B,N,K,D) gather of a cloud's k-NN neighbourhoods and what the reference's point-cloud regularisers compute
  * from it, without the gather; contract in DESIGN.md "k-NN edge operators".  points (B,N,D) fp32, idx int64 (B,N,K) as

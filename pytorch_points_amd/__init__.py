@@ -6,16 +6,16 @@ Drop-in for the reference's operator API on that path only:
     pytorch_points.network.operations.{gather_points, ball_query, grouping_operation, QueryAndGroup, batch_svd,
         normalize, sqrNorm, dot_product, cross_product_2D}
     pytorch_points.network.geo_operations.{furthest_point_sample, batch_normals, mean_value_coordinates_3D,
-        mean_value_coordinates, green_coordinates_3D, compute_face_normals_and_areas, pointUniformLaplacian, edge_vertex_indices,
-        get_edge_lengths}
+        mean_value_coordinates, green_coordinates_3D, green_coordinates_2D, compute_face_normals_and_areas,
+        pointUniformLaplacian, edge_vertex_indices, get_edge_lengths}
     pytorch_points.network.pointnet2_utils.{three_nn, three_interpolate, QueryAndGroup, GroupAll}
     pytorch_points.network.layers.{SharedMLP, Conv2d, Conv1d, Linear, ShuffleBlock, DenseEdgeConv,
         SampledDenseEdgeConv}
     pytorch_points.network.pointnet2_modules.{PointnetSAModuleMSG, PointnetSAModule, PointnetFPModule}
     pytorch_points._ext.{losses, sampling, linalg}
-mean_value_coordinates_3D, mean_value_coordinates and green_coordinates_3D also accept CPU tensors and other dtypes,
-through torch compositions of their contracts (pytorch_points_amd.mvc.composition, pytorch_points_amd.mvc2d.composition,
-pytorch_points_amd.green.composition).  The EdgeConv modules build their edge tensor with
+mean_value_coordinates_3D, mean_value_coordinates, green_coordinates_3D and green_coordinates_2D also accept CPU tensors
+and other dtypes, through torch compositions of their contracts (pytorch_points_amd.mvc.composition,
+pytorch_points_amd.mvc2d.composition, pytorch_points_amd.green.composition, pytorch_points_amd.green2d.composition).  The EdgeConv modules build their edge tensor with
 pytorch_points_amd.edge_features.knn_edge_features (fused HIP forward and backward for CUDA fp32, fp16 and bf16; its
 composition elsewhere).
 Host code is Python on PyTorch-ROCm (device memory, streams, torch.distributed); the kernels are

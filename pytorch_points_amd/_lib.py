@@ -95,6 +95,13 @@ SIGNATURES = {
     "pp_mvc2d_forward_f64": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pp_mvc2d_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
     "pp_mvc2d_backward_f64": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_gc2d_workspace_bytes": [_I, _I, _I, _I],
+    "pp_gc2d_forward_f32": [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_gc2d_forward_f64": [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_gc2d_backward_f32": [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _c_size_t,
+                             _P],
+    "pp_gc2d_backward_f64": [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _c_size_t,
+                             _P],
     "pp_knn_edges_workspace_bytes": [_I, _I, _I],
     "pp_knn_edge_lengths_forward_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "pp_knn_edge_lengths_backward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
@@ -127,6 +134,7 @@ _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_byte
              "pp_three_nn_workspace_bytes": _c_size_t, "pp_knn_workspace_bytes": _c_size_t,
              "pp_shard_packed_bytes": _c_size_t, "pp_mvc3d_workspace_bytes": _c_size_t,
              "pp_gc3d_workspace_bytes": _c_size_t, "pp_mvc2d_workspace_bytes": _c_size_t,
+             "pp_gc2d_workspace_bytes": _c_size_t,
              "pp_knn_edges_workspace_bytes": _c_size_t, "pp_edge_features_workspace_bytes": _c_size_t,
              "pp_mesh_edges_workspace_bytes": _c_size_t}
 

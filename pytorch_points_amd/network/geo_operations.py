@@ -1,21 +1,23 @@
 """Drop-in for the hot-path names of ``pytorch_points.network.geo_operations``: FurthestPointSampling /
 furthest_point_sample (reference network/geo_operations.py:11-64), the PCA point normals batch_normals
 (:88-126), the cage coordinates mean_value_coordinates_3D (:349-456), mean_value_coordinates (:459-526, the 2-D
-polygon cage) and green_coordinates_3D (:625-773), and the
-face normals those need, compute_face_normals_and_areas (:529-559), the point-cloud Laplacian
+polygon cage) and green_coordinates_3D (:625-773), green_coordinates_2D (:622, declared and left empty in the
+reference: the contract is this project's, DESIGN.md "Green coordinates, 2-D") with deform_with_green_coordinates_2D,
+and the face normals those need, compute_face_normals_and_areas (:529-559), the point-cloud Laplacian
 pointUniformLaplacian (:128-152), the mesh Laplacians UniformLaplacian, CotLaplacian and cotangent (:155-346), and
 the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600), and the face-to-face angles get_normals
 (:603-619, without its stray check_values line) and dihedral_angle (:775-789) with the (E,4) table they work on,
 get_edge_points (utils/geometry_utils.py:242-341: build_gemm, get_edge_points, get_side_points), and the mesh normals
 mesh_face_normals / mesh_vertex_normals (the reference has no vertex normals) with normalize_to_same_area
 (utils/geometry_utils.py:15-25).
-Only green_coordinates_2D, an empty stub in the reference, stays out."""
+Every function of the reference's geo_operations.py is served."""
 import collections
 
 import numpy as np
 import torch
 
 from .. import green as _green
+from .. import green2d as _green2d
 from .. import knn_edges as _knn_edges
 from .. import _mesh_topology
 from .. import mesh_dihedral as _mesh_dihedral
@@ -151,6 +153,22 @@ def green_coordinates_3D(query, vertices, faces, face_normals=None, verbose=Fals
     run fused HIP kernels; other devices and dtypes a torch composition of the same contract
     (pytorch_points_amd.green, DESIGN.md "Green coordinates")."""
     return _green.green_coordinates_3D(query, vertices, faces, face_normals, verbose)
+
+
+def green_coordinates_2D(query, vertices, faces, edge_normals=None, verbose=False):
+    """Green coordinates (Lipman et al. 2008) of ``query`` (B,P,2) with respect to the polygonal cage ``vertices``
+    (B,N,2), ``faces`` (B,F,2) (row ``j`` the directed edge ``(v1, v2)``; outer loops counter-clockwise, holes
+    clockwise): ``(phi (B,P,N), psi (B,P,F), exterior_flag (B,P,1))``.  ``edge_normals`` (B,F,2) only orients the
+    edges; ``verbose`` is ignored.  CUDA fp32 / fp64 run fused HIP kernels; other devices and dtypes a torch
+    composition of the same contract (pytorch_points_amd.green2d, DESIGN.md "Green coordinates, 2-D")."""
+    return _green2d.green_coordinates_2D(query, vertices, faces, edge_normals, verbose)
+
+
+def deform_with_green_coordinates_2D(phi, psi, vertices, new_vertices, faces):
+    """``sum_i phi_i v'_i + sum_j psi_j s_j n'_j`` (B,P,2): the queries of ``green_coordinates_2D`` carried along as
+    the cage ``vertices`` moves to ``new_vertices``, ``s_j`` the stretch of edge ``j`` and ``n'_j`` its deformed
+    normal (pytorch_points_amd.green2d).  Plain torch, differentiable."""
+    return _green2d.deform_with_green_coordinates_2D(phi, psi, vertices, new_vertices, faces)
 
 
 def pointUniformLaplacian(points, knn_idx=None, nn_size=3):
