@@ -298,6 +298,15 @@ def ptr(t):
     return _c_void_p(t.data_ptr())
 
 
+def faces_arg(faces, B, F, width):
+    """int64 faces (or edges) of ``width`` indices as the cage kernels read them: ``(tensor, batch stride in
+    elements)``.  A batch-expanded view of one list (stride 0 on B) is passed as that one list."""
+    fl = faces if faces.dtype == torch.int64 else faces.long()
+    if B > 1 and fl.stride(0) == 0:
+        return fl[0].contiguous(), 0
+    return fl.contiguous(), F * width
+
+
 # the cheap forms of torch.cuda.current_device() / is_current_stream_capturing() / current_stream().cuda_stream
 # (the public wrappers cost a microsecond each; an operator call makes several)
 try:

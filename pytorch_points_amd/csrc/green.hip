@@ -23,13 +23,12 @@
 // floating-point atomics anywhere: every output is reproducible bit for bit.
 #include <math.h>
 
-#include "pp_common.h"
+#include "cage_common.h"
+
+using namespace pp::cage;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kStride = 65;                 // LDS column stride (words of T)
-constexpr int kMaxLds = 160 * 1024;         // LDS per workgroup on gfx950
 #ifndef GC_DUAL_K
 #define GC_DUAL_K 3
 #endif
@@ -340,15 +339,6 @@ __device__ __forceinline__ void gc_pair(const S v[3][3], const S n[3], S& psi, S
 // code bits of a query row
 constexpr int kBadIndex = 8;
 
-__device__ __forceinline__ bool faces_ok(const long long* fb, int F, int N) {
-  bool ok = true;
-  for (int i = 0; i < F * 3; ++i) {
-    const long long x = fb[i];
-    ok = ok && x >= 0 && x < N;
-  }
-  return ok;
-}
-
 template <typename T>
 __device__ __forceinline__ void load_face(const long long* fb, const T* vtx, const T* nb, int f, const double q[3],
                                           int ix[3], double v[3][3], double n[3]) {
@@ -362,9 +352,6 @@ __device__ __forceinline__ void load_face(const long long* fb, const T* vtx, con
   for (int a = 0; a < 3; ++a) n[a] = (double)nb[(long long)f * 3 + a];
 }
 
-__device__ __forceinline__ float m_nan(float) { return __builtin_nanf(""); }
-__device__ __forceinline__ double m_nan(double) { return __builtin_nan(""); }
-
 template <typename T, bool LDS>
 __global__ __launch_bounds__(kWave) void gc_forward_kernel(const T* __restrict__ query, const T* __restrict__ vertices,
                                                            const long long* __restrict__ faces, long long fsb,
@@ -372,11 +359,7 @@ __global__ __launch_bounds__(kWave) void gc_forward_kernel(const T* __restrict__
                                                            T* __restrict__ gcf, T* __restrict__ sums,
                                                            int* __restrict__ codes, int P, int N, int F) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int lane = threadIdx.x, b = blockIdx.y;
-  const int p0 = blockIdx.x * kWave, p = p0 + lane;
-  const int rows = min(kWave, P - p0);
-  const bool live = p < P;
-  const long long row = (long long)b * P + (live ? p : P - 1);
+  const auto [lane, b, p0, p, rows, live, row] = tile_of(P);
   T* tile = (T*)smem;                                         // face coordinates of 64 faces, tile[fi * 65 + lane]
   T* acc = LDS ? tile + kWave * kStride + lane : gcv + row * N;
   const long long as = LDS ? kStride : 1;
@@ -384,7 +367,7 @@ __global__ __launch_bounds__(kWave) void gc_forward_kernel(const T* __restrict__
   const T* vtx = vertices + (long long)b * N * 3;
   const T* nb = normals + (long long)b * F * 3;
   const long long* fb = faces + (long long)b * fsb;
-  if (!faces_ok(fb, F, N)) {                                   // the whole batch element: NaN rows
+  if (!faces_ok<3>(fb, F, N)) {                                // the whole batch element: NaN rows
     if (live) {
       for (int j = 0; j < N; ++j) gcv[row * N + j] = m_nan(T(0));
       for (int f = 0; f < F; ++f) gcf[row * F + f] = m_nan(T(0));
@@ -409,8 +392,7 @@ __global__ __launch_bounds__(kWave) void gc_forward_kernel(const T* __restrict__
         for (int k = 0; k < 3; ++k) acc[ix[k] * as] += (T)phi[k];
     }
     __syncthreads();
-    for (int r = 0; r < rows; ++r)
-      if (lane < nf) gcf[((long long)b * P + p0 + r) * F + f0 + lane] = tile[lane * kStride + r];
+    tile_out(tile, rows, nf, lane, gcf + f0, (long long)b * P + p0, F);
     __syncthreads();
   }
   T sum = T(0);
@@ -425,20 +407,8 @@ __global__ __launch_bounds__(kWave) void gc_forward_kernel(const T* __restrict__
   }
   if (LDS) {
     __syncthreads();
-    const T* lds = tile + kWave * kStride;
-    for (int r = 0; r < rows; ++r) {
-      T* o = gcv + ((long long)b * P + p0 + r) * N;
-      for (int j = lane; j < N; j += kWave) o[j] = lds[j * kStride + r];
-    }
+    columns_to_rows(tile + kWave * kStride, rows, N, lane, gcv, (long long)b * P + p0, N);
   }
-}
-
-// sum over the wave; every lane returns the same bits (lane i and its partner add the same two values)
-__device__ __forceinline__ void wave_sum3(double (&x)[3]) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) x[i] += __shfl_xor(x[i], off, kWave);
 }
 
 // dL/d(query, normal) of one pair: W the cotangents of phi (3) and psi; gq, gn accumulate
@@ -484,28 +454,22 @@ __global__ __launch_bounds__(kWave) void gc_backward_kernel(
     const T* __restrict__ ggcv, const T* __restrict__ ggcf, T* __restrict__ gq, T* __restrict__ part, int P, int N,
     int F) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int lane = threadIdx.x, b = blockIdx.y, tiles = gridDim.x;
-  const int p0 = blockIdx.x * kWave, p = p0 + lane;
-  const int rows = min(kWave, P - p0);
-  const bool live = p < P;
-  const long long row = (long long)b * P + (live ? p : P - 1);
+  const auto [lane, b, p0, p, rows, live, row] = tile_of(P);
+  const int tiles = gridDim.x;
   T* tile = (T*)smem;                                          // dL/dGC_face of 64 faces, tile[fi * 65 + lane]
   T* gcol = tile + kWave * kStride;                            // LDS: dL/dGC_vertex rows, column per lane
   T* out = part + ((long long)b * tiles + blockIdx.x) * F * 3;
   const T* vtx = vertices + (long long)b * N * 3;
   const T* nb = normals + (long long)b * F * 3;
   const long long* fb = faces + (long long)b * fsb;
-  if (codes[(long long)b * P] & kBadIndex) {                   // the whole batch element (gc_reduce_kernel: NaN)
+  if (codes[(long long)b * P] & kBadIndex) {                   // the whole batch element (reduce_kernel: NaN)
     if (live)
 #pragma unroll
       for (int a = 0; a < 3; ++a) gq[row * 3 + a] = m_nan(T(0));
     return;
   }
   if (LDS) {
-    for (int r = 0; r < rows; ++r) {
-      const T* g = ggcv + ((long long)b * P + p0 + r) * N;
-      for (int j = lane; j < N; j += kWave) gcol[j * kStride + r] = g[j];
-    }
+    rows_to_columns(ggcv, (long long)b * P + p0, N, rows, N, lane, gcol);
     __syncthreads();
   }
   const T* grow = LDS ? gcol + lane : ggcv + row * N;
@@ -520,8 +484,7 @@ __global__ __launch_bounds__(kWave) void gc_backward_kernel(
     const int nf = min(kWave, F - f0);
     if (ggcf) {
       __syncthreads();
-      for (int r = 0; r < rows; ++r)
-        if (lane < nf) tile[lane * kStride + r] = ggcf[((long long)b * P + p0 + r) * F + f0 + lane];
+      tile_in(tile, rows, nf, lane, ggcf + f0, (long long)b * P + p0, F);
       __syncthreads();
     }
     for (int fi = 0; fi < nf; ++fi) {
@@ -536,7 +499,7 @@ __global__ __launch_bounds__(kWave) void gc_backward_kernel(
         W[3] = ggcf ? (double)tile[fi * kStride + lane] : 0.0;
         pair_grad(v, n, W, gqa, gn);
       }
-      wave_sum3(gn);
+      wave_sum(gn);
       if (lane == 0)
 #pragma unroll
         for (int a = 0; a < 3; ++a) out[(long long)f * 3 + a] = (T)gn[a];
@@ -547,45 +510,24 @@ __global__ __launch_bounds__(kWave) void gc_backward_kernel(
     for (int a = 0; a < 3; ++a) gq[row * 3 + a] = (T)gqa[a];
 }
 
-// dL/dnormals[b] = the workgroups' slices of batch element b, added in workgroup order; NaN for a batch element whose
-// face list holds an out-of-range index
-template <typename T>
-__global__ void gc_reduce_kernel(const T* __restrict__ part, const int* __restrict__ codes, T* __restrict__ gn, int B,
-                                 int P, int F, int tiles) {
-  const long long f3 = (long long)F * 3;
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)B * f3) return;
-  const int b = (int)(i / f3);
-  const long long k = i - (long long)b * f3;
-  if (codes[(long long)b * P] & kBadIndex) {
-    gn[i] = m_nan(T(0));
-    return;
-  }
-  T s = T(0);
-  for (int t = 0; t < tiles; ++t) s += part[((long long)b * tiles + t) * f3 + k];
-  gn[i] = s;
-}
-
 template <typename T>
 size_t lds_bytes(int N) {
   return (size_t)(N + kWave) * kStride * sizeof(T);
 }
-
-bool bad_sizes(int B, int P, int N, int F) { return B < 0 || P < 0 || N < 0 || F < 0; }
 
 template <typename T>
 int forward(const T* query, const T* vertices, const long long* faces, long long fsb, const T* normals, T* gcv, T* gcf,
             T* sums, int* codes, int B, int P, int N, int F, void* stream) {
   if (bad_sizes(B, P, N, F) || fsb < 0) return PP_EINVAL;
   if ((long long)B * P == 0) return PP_OK;
+  if (!grid_ok(B)) return PP_EINVAL;
   if (!query || !sums || !codes || (N > 0 && (!vertices || !gcv)) || (F > 0 && (!faces || !normals || !gcf)))
     return PP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((P + kWave - 1) / kWave), (unsigned)B);
+  const dim3 grid((unsigned)tiles_of(P), (unsigned)B);
   static pp::DeviceFlags flags;
   const size_t lds = lds_bytes<T>(N), tile = lds_bytes<T>(0);
-  if (lds <= (size_t)kMaxLds &&
-      (lds <= 65536 || pp::allow_big_lds(gc_forward_kernel<T, true>, (int)lds, flags) == hipSuccess))
+  if (lds_fits(gc_forward_kernel<T, true>, lds, flags))
     gc_forward_kernel<T, true><<<grid, dim3(kWave), lds, st>>>(query, vertices, faces, fsb, normals, gcv, gcf, sums,
                                                                 codes, P, N, F);
   else
@@ -593,11 +535,6 @@ int forward(const T* query, const T* vertices, const long long* faces, long long
                                                                   codes, P, N, F);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
-}
-
-size_t workspace_bytes(int B, int P, int F, int elem) {
-  if (B <= 0 || P <= 0 || F <= 0) return 0;
-  return (size_t)B * ((P + kWave - 1) / kWave) * F * 3 * elem;
 }
 
 template <typename T>
@@ -613,15 +550,15 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
   }
   if (!query || !sums || !codes || !gq || (N > 0 && (!vertices || !gcv || !ggcv))) return PP_EINVAL;
   if (F == 0) return (int)pp::fill_bytes(gq, 0, (size_t)B * P * 3 * sizeof(T), st);
-  const size_t need = workspace_bytes(B, P, F, (int)sizeof(T));
+  if (!grid_ok(B)) return PP_EINVAL;
+  const size_t need = workspace_bytes(B, P, F, 3, (int)sizeof(T));
   if (!faces || !normals || !ws || ws_bytes < need) return PP_EINVAL;
   T* part = (T*)ws;
-  const int tiles = (P + kWave - 1) / kWave;
+  const int tiles = tiles_of(P);
   const dim3 grid((unsigned)tiles, (unsigned)B);
   static pp::DeviceFlags flags;
   const size_t lds = lds_bytes<T>(N), tile = lds_bytes<T>(0);
-  if (lds <= (size_t)kMaxLds &&
-      (lds <= 65536 || pp::allow_big_lds(gc_backward_kernel<T, true>, (int)lds, flags) == hipSuccess))
+  if (lds_fits(gc_backward_kernel<T, true>, lds, flags))
     gc_backward_kernel<T, true><<<grid, dim3(kWave), lds, st>>>(query, vertices, faces, fsb, normals, gcv, sums, codes,
                                                                  ggcv, ggcf, gq, part, P, N, F);
   else
@@ -629,7 +566,9 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
                                                                    codes, ggcv, ggcf, gq, part, P, N, F);
   PP_RETURN_IF_LAUNCH_FAILED();
   const long long n = (long long)B * F * 3;
-  gc_reduce_kernel<T><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(part, codes, gn, B, P, F, tiles);
+  // dL/dnormals[b]: the workgroups' slices in workgroup order; NaN where the face list holds an out-of-range index
+  reduce_kernel<T><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(part, codes, gn, B, P, (long long)F * 3,
+                                                                            tiles, kBadIndex);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }
@@ -638,7 +577,7 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
 
 extern "C" size_t pp_gc3d_workspace_bytes(int B, int P, int F, int elem_bytes) {
   if (elem_bytes != 4 && elem_bytes != 8) return 0;
-  return workspace_bytes(B, P, F, elem_bytes);
+  return workspace_bytes(B, P, F, 3, elem_bytes);
 }
 
 extern "C" int pp_gc3d_forward_f32(const float* query, const float* vertices, const long long* faces,

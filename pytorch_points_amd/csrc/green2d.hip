@@ -20,31 +20,17 @@
 // slice of the workspace; a second kernel adds the slices of a batch element in workgroup order; a third, one thread
 // per vertex, collects the vertex's edge ends in ascending edge order (a scan of all F edges per vertex: cages are
 // small).  No floating-point atomics anywhere: every output is reproducible bit for bit.
-#include <limits.h>
 #include <math.h>
 
-#include "pp_common.h"
+#include "cage_common.h"
+
+using namespace pp::cage;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kStride = 65;                 // LDS column stride (elements)
-constexpr int kMaxLds = 160 * 1024;         // LDS per workgroup on gfx950
 constexpr double kPi = 3.14159265358979323846;
 // code bits of a query row
 constexpr int kNonFinite = 1, kBadIndex = 8;
-
-__device__ __forceinline__ float m_nan(float) { return __builtin_nanf(""); }
-__device__ __forceinline__ double m_nan(double) { return __builtin_nan(""); }
-
-__device__ __forceinline__ bool faces_ok(const long long* fb, int F, int N) {
-  bool ok = true;
-  for (int i = 0; i < F * 2; ++i) {
-    const long long x = fb[i];
-    ok = ok && x >= 0 && x < N;
-  }
-  return ok;
-}
 
 // edge j as the pair evaluation takes it: reversed where the given normal points against the edge's own
 struct Edge {
@@ -127,7 +113,8 @@ __device__ __forceinline__ bool finite3(double a, double b, double c) {
   return fabs(a) < INFINITY && fabs(b) < INFINITY && fabs(c) < INFINITY;
 }
 
-// LDS: acc (fp64, chunk columns), then the psi tile of 64 edges (T)
+// LDS: acc (fp64, chunk columns), then the psi tile of 64 edges (T).  The prologue and the two transposes are written
+// out here: on cage_common.h's helpers this kernel's fp64 form measured 1 % slower (profiles/cage_common/).
 template <typename T>
 __global__ __launch_bounds__(kWave) void gc2d_forward_kernel(
     const T* __restrict__ query, const T* __restrict__ vertices, const long long* __restrict__ faces, long long fsb,
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(kWave) void gc2d_forward_kernel(
   const T* vtx = vertices + (long long)b * N * 2;
   const T* en = normals ? normals + (long long)b * F * 2 : nullptr;
   const long long* fb = faces + (long long)b * fsb;
-  if (!faces_ok(fb, F, N)) {                                   // the whole batch element: NaN rows
+  if (!faces_ok<2>(fb, F, N)) {                                // the whole batch element: NaN rows
     if (live) {
       for (int j = 0; j < N; ++j) phi[row * N + j] = m_nan(T(0));
       for (int f = 0; f < F; ++f) psi[row * F + f] = m_nan(T(0));
@@ -197,14 +184,6 @@ __global__ __launch_bounds__(kWave) void gc2d_forward_kernel(
     exterior[row] = (!bad && sum < 0.5) ? 1 : 0;
     codes[row] = bad ? kNonFinite : 0;
   }
-}
-
-// sum over the wave; every lane returns the same bits (lane i and its partner add the same two values)
-__device__ __forceinline__ void wave_sum4(double (&x)[4]) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x[i] += __shfl_xor(x[i], off, kWave);
 }
 
 // dL/d(v1, v2) of one pair into gv (x1, y1, x2, y2), -dL/dquery's share subtracted from gq: w1, w2, wp the
@@ -262,11 +241,8 @@ __global__ __launch_bounds__(kWave) void gc2d_backward_kernel(
     const T* __restrict__ normals, const int* __restrict__ codes, const T* __restrict__ gphi,
     const T* __restrict__ gpsi, T* __restrict__ gq, T* __restrict__ part, int P, int N, int F) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int lane = threadIdx.x, b = blockIdx.y, tiles = gridDim.x;
-  const int p0 = blockIdx.x * kWave, p = p0 + lane;
-  const int rows = min(kWave, P - p0);
-  const bool live = p < P;
-  const long long row = (long long)b * P + (live ? p : P - 1);
+  const auto [lane, b, p0, p, rows, live, row] = tile_of(P);
+  const int tiles = gridDim.x;
   T* tile = (T*)smem;                                          // tile[fi * 65 + lane]
   T* gcol = tile + kWave * kStride;                            // gcol[v * 65 + lane]
   T* out = part + ((long long)b * tiles + blockIdx.x) * F * 4;
@@ -278,10 +254,7 @@ __global__ __launch_bounds__(kWave) void gc2d_backward_kernel(
     return;
   }
   if (LDS && gphi) {
-    for (int r = 0; r < rows; ++r) {
-      const T* g = gphi + ((long long)b * P + p0 + r) * N;
-      for (int j = lane; j < N; j += kWave) gcol[j * kStride + r] = g[j];
-    }
+    rows_to_columns(gphi, (long long)b * P + p0, N, rows, N, lane, gcol);
     __syncthreads();
   }
   const T* grow = LDS ? gcol + lane : (gphi ? gphi + row * N : nullptr);
@@ -292,8 +265,7 @@ __global__ __launch_bounds__(kWave) void gc2d_backward_kernel(
     const int nf = min(kWave, F - f0);
     if (gpsi) {
       __syncthreads();
-      for (int r = 0; r < rows; ++r)
-        if (lane < nf) tile[lane * kStride + r] = gpsi[((long long)b * P + p0 + r) * F + f0 + lane];
+      tile_in(tile, rows, nf, lane, gpsi + f0, (long long)b * P + p0, F);
       __syncthreads();
     }
     for (int fi = 0; fi < nf; ++fi) {
@@ -306,7 +278,7 @@ __global__ __launch_bounds__(kWave) void gc2d_backward_kernel(
         const double wp = gpsi ? (double)tile[fi * kStride + lane] : 0.0;
         pair_grad(pr, w1, w2, wp, gv, gqa);
       }
-      wave_sum4(gv);
+      wave_sum(gv);
       if (lane == 0) {                                         // in the order of the edge's row of faces
         const int s1 = E.flip ? 2 : 0, s2 = E.flip ? 0 : 2;
         out[(long long)f * 4 + s1] = (T)gv[0];
@@ -376,19 +348,15 @@ constexpr int chunk_cap(size_t limit) {
   return (int)((limit - tile_bytes<T>()) / (kStride * sizeof(double)));
 }
 
-bool bad_sizes(int B, int P, int N, int F) {
-  return B < 0 || P < 0 || N < 0 || F < 0 || P > INT_MAX - kWave || F > INT_MAX / 4 || N > INT_MAX / kStride;
-}
-
 template <typename T>
 int forward(const T* query, const T* vertices, const long long* faces, long long fsb, const T* normals, T* phi, T* psi,
             unsigned char* exterior, int* codes, int B, int P, int N, int F, void* stream) {
   if (bad_sizes(B, P, N, F) || fsb < 0) return PP_EINVAL;
   if ((long long)B * P == 0) return PP_OK;
-  if (B > 65535) return PP_EINVAL;
+  if (!grid_ok(B)) return PP_EINVAL;
   if (!query || !exterior || !codes || (N > 0 && (!vertices || !phi)) || (F > 0 && (!faces || !psi))) return PP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((P + kWave - 1) / kWave), (unsigned)B);
+  const dim3 grid((unsigned)tiles_of(P), (unsigned)B);
   static pp::DeviceFlags flags;
   int chunk = N < 1 ? 1 : (N < chunk_cap<T>(kMaxLds) ? N : chunk_cap<T>(kMaxLds));
   size_t lds = (size_t)chunk * kStride * sizeof(double) + tile_bytes<T>();
@@ -400,11 +368,6 @@ int forward(const T* query, const T* vertices, const long long* faces, long long
                                                          codes, P, N, F, chunk);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
-}
-
-size_t workspace_bytes(int B, int P, int F, int elem) {
-  if (B <= 0 || P <= 0 || F <= 0 || P > INT_MAX - kWave) return 0;
-  return (size_t)B * ((P + kWave - 1) / kWave) * F * 4 * elem;
 }
 
 template <typename T>
@@ -420,16 +383,15 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
     if (e == hipSuccess) e = pp::fill_bytes(gq, 0, (size_t)B * P * 2 * sizeof(T), st);
     return (int)e;
   }
-  if (B > 65535) return PP_EINVAL;
-  const size_t need = workspace_bytes(B, P, F, (int)sizeof(T));
+  if (!grid_ok(B)) return PP_EINVAL;
+  const size_t need = workspace_bytes(B, P, F, 4, (int)sizeof(T));
   if (!query || !codes || !faces || (N > 0 && !vertices) || !ws || ws_bytes < need) return PP_EINVAL;
   T* part = (T*)ws;
-  const int tiles = (P + kWave - 1) / kWave;
+  const int tiles = tiles_of(P);
   const dim3 grid((unsigned)tiles, (unsigned)B);
   static pp::DeviceFlags flags;
   const size_t tile = tile_bytes<T>(), lds = tile + (size_t)N * kStride * sizeof(T);
-  if (lds <= (size_t)kMaxLds &&
-      (lds <= 65536 || pp::allow_big_lds(gc2d_backward_kernel<T, true>, (int)lds, flags) == hipSuccess))
+  if (lds_fits(gc2d_backward_kernel<T, true>, lds, flags))
     gc2d_backward_kernel<T, true><<<grid, dim3(kWave), lds, st>>>(query, vertices, faces, fsb, normals, codes, gphi,
                                                                    gpsi, gq, part, P, N, F);
   else
@@ -452,7 +414,7 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
 
 extern "C" size_t pp_gc2d_workspace_bytes(int B, int P, int F, int elem_bytes) {
   if (elem_bytes != 4 && elem_bytes != 8) return 0;
-  return workspace_bytes(B, P, F, elem_bytes);
+  return workspace_bytes(B, P, F, 4, elem_bytes);
 }
 
 extern "C" int pp_gc2d_forward_f32(const float* query, const float* vertices, const long long* faces,

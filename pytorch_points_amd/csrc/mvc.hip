@@ -17,21 +17,17 @@
 // No floating-point atomics anywhere: every output is reproducible bit for bit.
 #include <math.h>
 
-#include "pp_common.h"
+#include "cage_common.h"
+
+using namespace pp::cage;
 
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kStride = 65;                 // LDS column stride (words of T)
-constexpr int kMaxLds = 160 * 1024;         // LDS per workgroup on gfx950
 
 __device__ __forceinline__ float m_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double m_sqrt(double x) { return sqrt(x); }
 __device__ __forceinline__ double m_asin(double x) { return asin(x); }
 __device__ __forceinline__ void m_sincos(double x, double* s, double* c) { sincos(x, s, c); }
 __device__ __forceinline__ double m_sin(double x) { return sin(x); }
-__device__ __forceinline__ float m_nan(float) { return __builtin_nanf(""); }
-__device__ __forceinline__ double m_nan(double) { return __builtin_nan(""); }
 
 template <typename T>
 __device__ __forceinline__ T norm3(T x, T y, T z) {
@@ -225,11 +221,8 @@ __global__ __launch_bounds__(kWave) void mvc_forward_kernel(const T* __restrict_
                                                             int* __restrict__ codes, T* __restrict__ wi, int P, int N,
                                                             int F) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int lane = threadIdx.x, b = blockIdx.y;
-  const int p = blockIdx.x * kWave + lane;
-  const bool live = p < P;
+  const auto [lane, b, p0, p, rows, live, row] = tile_of(P);
   if (!LDS && !live) return;                        // the general path has no cross-lane step
-  const long long row = (long long)b * P + (live ? p : P - 1);
   T* acc = LDS ? (T*)smem + lane : out + row * N;
   const long long as = LDS ? kStride : 1;
   const T* vtx = vertices + (long long)b * N * 3;
@@ -303,17 +296,13 @@ __global__ __launch_bounds__(kWave) void mvc_forward_kernel(const T* __restrict_
   }
   if (LDS) {
     __syncthreads();
-    const T* lds = (const T*)smem;
-    const int rows = min(kWave, P - (int)blockIdx.x * kWave);
-    for (int r = 0; r < rows; ++r) {
-      T* o = out + ((long long)b * P + (long long)blockIdx.x * kWave + r) * N;
-      for (int j = lane; j < N; j += kWave) o[j] = lds[j * kStride + r];
-    }
+    columns_to_rows((const T*)smem, rows, N, lane, out, (long long)b * P + p0, N);
   }
 }
 
-// sum over the wave of nine values; every lane returns the same bits
-__device__ __forceinline__ void wave_sum9(float (&x)[9]) {
+// the fp32 form of the wave sum of nine values (cage_common.h has the fp64 one): DPP, every lane returns the same bits
+using pp::cage::wave_sum;
+__device__ __forceinline__ void wave_sum(float (&x)[9]) {
   float a[6] = {x[0], x[1], x[2], x[3], x[4], x[5]};
   float c[6] = {x[6], x[7], x[8], 0.f, 0.f, 0.f};
   pp::wave_reduce6_dpp<true, 6>(a);
@@ -323,13 +312,6 @@ __device__ __forceinline__ void wave_sum9(float (&x)[9]) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) x[6 + i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c[i]), 63));
 }
-__device__ __forceinline__ void wave_sum9(double (&x)[9]) {
-  // xor butterfly: lane i and its partner add the same two values (a + b == b + a), so all lanes agree
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-    for (int i = 0; i < 9; ++i) x[i] += __shfl_xor(x[i], off, kWave);
-}
 
 template <typename T, bool LDS>
 __global__ __launch_bounds__(kWave) void mvc_backward_kernel(
@@ -337,11 +319,9 @@ __global__ __launch_bounds__(kWave) void mvc_backward_kernel(
     const T* __restrict__ wj, const T* __restrict__ sums, const int* __restrict__ codes, const T* __restrict__ gwj,
     const T* __restrict__ gwi, T* __restrict__ gq, T* __restrict__ part, int P, int N, int F) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int lane = threadIdx.x, b = blockIdx.y, tiles = gridDim.x;
-  const int p = blockIdx.x * kWave + lane;
-  const bool live = p < P;
-  const long long row = (long long)b * P + (live ? p : P - 1);
-  T* gcol = (T*)smem;                                          // LDS: dL/dwj rows, column per lane
+  const auto [lane, b, p0, p, rows, live, row] = tile_of(P);
+  const int tiles = gridDim.x;
+  T* gcol = (T*)smem;                                         // LDS: dL/dwj rows, column per lane
   T* dv = LDS ? gcol + (long long)N * kStride : part + ((long long)b * tiles + blockIdx.x) * N * 3;
   const T* vtx = vertices + (long long)b * N * 3;
   const long long* fb = faces + (long long)b * fsb;
@@ -350,11 +330,7 @@ __global__ __launch_bounds__(kWave) void mvc_backward_kernel(
   const bool dead = !live || (code & (kOnVertex | kBadIndex));  // rows overridden to constants: no gradient
   if (LDS) {
     for (int i = lane; i < N * 3; i += kWave) dv[i] = T(0);
-    const int rows = min(kWave, P - (int)blockIdx.x * kWave);
-    for (int r = 0; r < rows; ++r) {
-      const T* g = gwj + ((long long)b * P + (long long)blockIdx.x * kWave + r) * N;
-      for (int j = lane; j < N; j += kWave) gcol[j * kStride + r] = g[j];
-    }
+    rows_to_columns(gwj, (long long)b * P + p0, N, rows, N, lane, gcol);
     __syncthreads();
   }
   const T* grow = LDS ? gcol + lane : gwj + row * N;
@@ -397,7 +373,7 @@ __global__ __launch_bounds__(kWave) void mvc_backward_kernel(
           }
       }
     }
-    wave_sum9(gu);
+    wave_sum(gu);
     if (lane == 0)
 #pragma unroll
       for (int k = 0; k < 3; ++k)
@@ -414,22 +390,6 @@ __global__ __launch_bounds__(kWave) void mvc_backward_kernel(
   }
 }
 
-// dL/dvertices[b] = the workgroups' partials of batch element b, added in workgroup order; NaN for a batch element
-// whose face list holds an out-of-range index
-template <typename T>
-__global__ void mvc_reduce_kernel(const T* __restrict__ part, const int* __restrict__ codes, T* __restrict__ gv, int B,
-                                  int P, int N, int tiles) {
-  const long long n3 = (long long)N * 3;
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)B * n3) return;
-  const int b = (int)(i / n3);
-  const long long k = i - (long long)b * n3;
-  T s = T(0);
-  for (int t = 0; t < tiles; ++t) s += part[((long long)b * tiles + t) * n3 + k];
-  if (P > 0 && (codes[(long long)b * P] & kBadIndex)) s = m_nan(T(0));
-  gv[i] = s;
-}
-
 template <typename T>
 size_t fwd_lds(int N) {
   return (size_t)N * kStride * sizeof(T);
@@ -439,30 +399,23 @@ size_t bwd_lds(int N) {
   return (size_t)N * (kStride + 3) * sizeof(T);
 }
 
-bool bad_sizes(int B, int P, int N, int F) { return B < 0 || P < 0 || N < 0 || F < 0; }
-
 template <typename T>
 int forward(const T* query, const T* vertices, const long long* faces, long long fsb, T* wj, T* sums, int* codes,
             T* wi, int B, int P, int N, int F, void* stream) {
   if (bad_sizes(B, P, N, F) || fsb < 0) return PP_EINVAL;
   if ((long long)B * P == 0) return PP_OK;
+  if (!grid_ok(B)) return PP_EINVAL;
   if (!query || !wj || !sums || !codes || (N > 0 && !vertices) || (F > 0 && !faces)) return PP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((P + kWave - 1) / kWave), (unsigned)B);
+  const dim3 grid((unsigned)tiles_of(P), (unsigned)B);
   static pp::DeviceFlags flags;
   const size_t lds = fwd_lds<T>(N);
-  if (N > 0 && lds <= (size_t)kMaxLds &&
-      (lds <= 65536 || pp::allow_big_lds(mvc_forward_kernel<T, true>, (int)lds, flags) == hipSuccess))
+  if (N > 0 && lds_fits(mvc_forward_kernel<T, true>, lds, flags))
     mvc_forward_kernel<T, true><<<grid, dim3(kWave), lds, st>>>(query, vertices, faces, fsb, wj, sums, codes, wi, P, N, F);
   else
     mvc_forward_kernel<T, false><<<grid, dim3(kWave), 0, st>>>(query, vertices, faces, fsb, wj, sums, codes, wi, P, N, F);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
-}
-
-size_t workspace_bytes(int B, int P, int N, int elem) {
-  if (B <= 0 || P <= 0 || N <= 0) return 0;
-  return (size_t)B * ((P + kWave - 1) / kWave) * N * 3 * elem;
 }
 
 template <typename T>
@@ -478,15 +431,15 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
   }
   if (!query || !wj || !sums || !codes || !gwj || !gq || (F > 0 && !faces)) return PP_EINVAL;
   if (N == 0) return (int)pp::fill_bytes(gq, 0, (size_t)B * P * 3 * sizeof(T), st);
-  const size_t need = workspace_bytes(B, P, N, (int)sizeof(T));
+  if (!grid_ok(B)) return PP_EINVAL;
+  const size_t need = workspace_bytes(B, P, N, 3, (int)sizeof(T));
   if (!ws || ws_bytes < need || !vertices) return PP_EINVAL;
   T* part = (T*)ws;
-  const int tiles = (P + kWave - 1) / kWave;
+  const int tiles = tiles_of(P);
   const dim3 grid((unsigned)tiles, (unsigned)B);
   static pp::DeviceFlags flags;
   const size_t lds = bwd_lds<T>(N);
-  if (lds <= (size_t)kMaxLds &&
-      (lds <= 65536 || pp::allow_big_lds(mvc_backward_kernel<T, true>, (int)lds, flags) == hipSuccess)) {
+  if (lds_fits(mvc_backward_kernel<T, true>, lds, flags)) {
     mvc_backward_kernel<T, true><<<grid, dim3(kWave), lds, st>>>(query, vertices, faces, fsb, wj, sums, codes, gwj, gwi,
                                                                   gq, part, P, N, F);
   } else {
@@ -497,7 +450,9 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
   }
   PP_RETURN_IF_LAUNCH_FAILED();
   const long long n = (long long)B * N * 3;
-  mvc_reduce_kernel<T><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(part, codes, gv, B, P, N, tiles);
+  // dL/dvertices[b]: the workgroups' partials in workgroup order; NaN where the face list holds an out-of-range index
+  reduce_kernel<T><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(part, codes, gv, B, P, (long long)N * 3,
+                                                                            tiles, kBadIndex);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }
@@ -506,7 +461,7 @@ int backward(const T* query, const T* vertices, const long long* faces, long lon
 
 extern "C" size_t pp_mvc3d_workspace_bytes(int B, int P, int N, int elem_bytes) {
   if (elem_bytes != 4 && elem_bytes != 8) return 0;
-  return workspace_bytes(B, P, N, elem_bytes);
+  return workspace_bytes(B, P, N, 3, elem_bytes);
 }
 
 extern "C" int pp_mvc3d_forward_f32(const float* query, const float* vertices, const long long* faces,

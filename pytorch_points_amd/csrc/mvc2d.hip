@@ -15,14 +15,14 @@
 // a vertex's dL/dpolygon is summed over the wave in a fixed order and stored by one lane into the workgroup's slice of
 // the workspace, and a second kernel adds the slices of a batch element in workgroup order.  No floating-point atomics:
 // every output is reproducible bit for bit, and a query's forward row does not depend on the other queries.
-#include <limits.h>
 #include <math.h>
 
-#include "pp_common.h"
+#include "cage_common.h"
+
+using namespace pp::cage;
 
 namespace {
 
-constexpr int kWave = 64;
 // code bits of a query row (kept for the backward)
 constexpr int kZeroSum = 1, kOnEdge = 2, kOnVertex = 4, kNonFinite = 8;
 constexpr double kAreaEps = 1e-5;    // |A_i| <= this: pair i contributes no t_i; with D_i < 0 the query is on edge i
@@ -159,10 +159,9 @@ __global__ __launch_bounds__(kWave) void mvc2d_forward_kernel(const T* __restric
 // sum over the wave in a fixed order; every lane returns the same bits
 __device__ __forceinline__ float wave_sum(float v) { return pp::wave_reduce_dpp<true>(v); }
 __device__ __forceinline__ double wave_sum(double v) {
-  // xor butterfly: lane i and its partner add the same two values (a + b == b + a), so all lanes agree
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
+  double x[1] = {v};
+  pp::cage::wave_sum(x);
+  return x[0];
 }
 
 template <typename T>
@@ -297,13 +296,9 @@ __global__ void mvc2d_reduce_kernel(const T* __restrict__ part, T* __restrict__ 
   gpolygon[idx] = s;
 }
 
-bool bad_sizes(int B, int N, int M) { return B < 0 || N < 0 || M < 0 || N > INT_MAX - kWave; }
-
-int tiles_of(int N) { return (N + kWave - 1) / kWave; }
-
 template <typename T>
 int forward(const T* points, const T* polygon, T* phi, T* w, T* sums, int* codes, int B, int N, int M, void* stream) {
-  if (bad_sizes(B, N, M)) return PP_EINVAL;
+  if (bad_sizes(B, N, M, 0)) return PP_EINVAL;
   if (B == 0 || N == 0 || M == 0) return PP_OK;
   if (!points || !polygon || !phi || !sums || !codes) return PP_EINVAL;
   const int tiles = tiles_of(N);
@@ -314,15 +309,10 @@ int forward(const T* points, const T* polygon, T* phi, T* w, T* sums, int* codes
   return PP_OK;
 }
 
-size_t workspace_bytes(int B, int N, int M, int elem) {
-  if (B <= 0 || N <= 0 || M <= 0 || N > INT_MAX - kWave) return 0;
-  return (size_t)B * tiles_of(N) * M * 2 * elem;
-}
-
 template <typename T>
 int backward(const T* points, const T* polygon, const T* phi, const T* sums, const int* codes, const T* gphi,
              const T* gw, T* gpoints, T* gpolygon, int B, int N, int M, void* ws, size_t ws_bytes, void* stream) {
-  if (bad_sizes(B, N, M)) return PP_EINVAL;
+  if (bad_sizes(B, N, M, 0)) return PP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (B == 0 || (N == 0 && M == 0)) return PP_OK;
   if (N == 0) {                                      // no query: the polygon's gradient is zero
@@ -336,7 +326,7 @@ int backward(const T* points, const T* polygon, const T* phi, const T* sums, con
   if (!points || !polygon || !phi || !sums || !codes || !gphi || !gpoints || !gpolygon) return PP_EINVAL;
   const int tiles = tiles_of(N);
   if ((long long)B * tiles > INT_MAX) return PP_EINVAL;
-  if (!ws || ws_bytes < workspace_bytes(B, N, M, (int)sizeof(T))) return PP_EINVAL;
+  if (!ws || ws_bytes < workspace_bytes(B, N, M, 2, (int)sizeof(T))) return PP_EINVAL;
   T* part = (T*)ws;
   mvc2d_backward_kernel<T><<<dim3((unsigned)(B * tiles)), dim3(kWave), 0, st>>>(points, polygon, phi, sums, codes,
                                                                                  gphi, gw, gpoints, part, N, M, tiles);
@@ -351,7 +341,7 @@ int backward(const T* points, const T* polygon, const T* phi, const T* sums, con
 
 extern "C" size_t pp_mvc2d_workspace_bytes(int B, int N, int M, int elem_bytes) {
   if (elem_bytes != 4 && elem_bytes != 8) return 0;
-  return workspace_bytes(B, N, M, elem_bytes);
+  return workspace_bytes(B, N, M, 2, elem_bytes);
 }
 
 extern "C" int pp_mvc2d_forward_f32(const float* points, const float* polygon, float* phi, float* w, float* sums,

@@ -166,15 +166,6 @@ def composition(query, vertices, faces, face_normals=None, verbose=False):
     return gcv, gcf, exterior & ~bad[:, None, None]
 
 
-def _faces_arg(faces, B, F):
-    """int64 faces as the kernels read them: ``(tensor, batch stride in elements)``.  A batch-expanded view of one
-    face list (stride 0 on B) is passed as that one list."""
-    fl = faces if faces.dtype == torch.int64 else faces.long()
-    if B > 1 and fl.stride(0) == 0:
-        return fl[0].contiguous(), 0
-    return fl.contiguous(), F * 3
-
-
 class GreenCoordinates3D(torch.autograd.Function):
     """HIP forward and backward (CUDA fp32 / fp64) of the pair evaluation, for the vertices detached: inputs
     ``(query, vertices, faces, n_t)``, outputs ``(GC_vertex, GC_face, exterior_flag)``; gradients reach ``query`` and
@@ -189,7 +180,7 @@ class GreenCoordinates3D(torch.autograd.Function):
         query = query.contiguous()
         vertices = vertices.contiguous()
         n_t = n_t.contiguous()
-        fl, fsb = _faces_arg(faces, B, F)
+        fl, fsb = _lib.faces_arg(faces, B, F, 3)
         gcv = torch.empty(B, P, N, dtype=dt, device=dev)
         gcf = torch.empty(B, P, F, dtype=dt, device=dev)
         sums = torch.empty(B, P, dtype=dt, device=dev)

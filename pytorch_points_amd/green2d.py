@@ -115,15 +115,6 @@ def composition(query, vertices, faces, edge_normals=None, verbose=False):
     return phi, psi, (total < 0.5) & ~dead
 
 
-def _faces_arg(faces, B, F):
-    """int64 edges as the kernels read them: ``(tensor, batch stride in elements)``.  A batch-expanded view of one
-    edge list (stride 0 on B) is passed as that one list."""
-    fl = faces if faces.dtype == torch.int64 else faces.long()
-    if B > 1 and fl.stride(0) == 0:
-        return fl[0].contiguous(), 0
-    return fl.contiguous(), F * 2
-
-
 class GreenCoordinates2D(torch.autograd.Function):
     """HIP forward and backward (CUDA fp32 / fp64): inputs ``(query, vertices, faces, edge_normals or None)``,
     outputs ``(phi, psi, exterior_flag)``; gradients reach ``query`` and ``vertices``."""
@@ -140,7 +131,7 @@ class GreenCoordinates2D(torch.autograd.Function):
         query = query.contiguous()
         vertices = vertices.contiguous()
         en = edge_normals.detach().contiguous() if edge_normals is not None else None
-        fl, fsb = _faces_arg(faces, B, F)
+        fl, fsb = _lib.faces_arg(faces, B, F, 2)
         phi = torch.empty(B, P, N, dtype=dt, device=dev)
         psi = torch.empty(B, P, F, dtype=dt, device=dev)
         exterior = torch.empty(B, P, 1, dtype=torch.bool, device=dev)

@@ -105,15 +105,6 @@ def composition(query, vertices, faces, verbose=False):
     return wj, wi
 
 
-def _faces_arg(faces, B, F):
-    """int64 faces as the kernels read them: ``(tensor, batch stride in elements)``.  A batch-expanded view of one
-    face list (stride 0 on B) is passed as that one list."""
-    fl = faces if faces.dtype == torch.int64 else faces.long()
-    if B > 1 and fl.stride(0) == 0:
-        return fl[0].contiguous(), 0
-    return fl.contiguous(), F * 3
-
-
 class MeanValueCoordinates3D(torch.autograd.Function):
     """HIP forward and backward (CUDA fp32 / fp64).  Outputs ``wj`` and, with ``verbose``, ``wi``."""
 
@@ -125,7 +116,7 @@ class MeanValueCoordinates3D(torch.autograd.Function):
         N, F = vertices.shape[1], faces.shape[1]
         query = query.contiguous()
         vertices = vertices.contiguous()
-        fl, fsb = _faces_arg(faces, B, F)
+        fl, fsb = _lib.faces_arg(faces, B, F, 3)
         wj = torch.empty(B, P, N, dtype=dt, device=dev)
         sums = torch.empty(B, P, dtype=dt, device=dev)
         codes = torch.empty(B, P, dtype=torch.int32, device=dev)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from cage_checks import rel_close
 from pytorch_points_amd import green
 
 pytestmark = pytest.mark.gpu
@@ -50,12 +51,6 @@ def run(fn, q, v, f, Gv=None, Gf=None, n=None):
 
 kern = green.green_coordinates_3D
 comp = green.composition
-
-
-def rel_close(got, ref, rtol):
-    scale = max(1.0, float(np.abs(ref).max(initial=0.0)))
-    err = np.abs(got - ref).max(initial=0.0)
-    assert err <= rtol * scale, (err, scale)
 
 
 def row_err(got, ref):

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+from cage_checks import rel_close, same_bits
 from pytorch_points_amd import mvc
 
 pytestmark = pytest.mark.gpu
@@ -62,12 +63,6 @@ def comp(q, v, f, G=None, verbose=True):
     if G is not None:
         res += list(torch.autograd.grad((wj * G).sum(), (q, v)))
     return [t.cpu().numpy() for t in res]
-
-
-def rel_close(got, ref, rtol):
-    scale = max(1.0, float(np.abs(ref).max(initial=0.0)))
-    err = np.abs(got - ref).max(initial=0.0)
-    assert err <= rtol * scale, (err, scale)
 
 
 # --------------------------------------------------------------------------------------------- golden fixtures
@@ -283,11 +278,6 @@ def path_baseline(dev, dtype):
     Gwi = torch.randn(3, PATH_P, len(f0), 3, dtype=dtype, device=dev, generator=gen)
     q, v = torch.from_numpy(q).to(dev, dtype), torch.from_numpy(v).to(dev, dtype)
     return G, Gwi, run(q, v, path_faces(dev, "expanded"), G[..., :PATH_CAGE_N], Gwi=Gwi)
-
-
-def same_bits(x, y):
-    it = {4: np.int32, 8: np.int64}[x.dtype.itemsize]
-    return x.shape == y.shape and np.array_equal(np.ascontiguousarray(x).view(it), np.ascontiguousarray(y).view(it))
 
 
 @pytest.mark.parametrize("faces", ["expanded", "per_batch"])

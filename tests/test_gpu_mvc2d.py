@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from cage_checks import same_bits
 from pytorch_points_amd import mvc2d
 
 pytestmark = pytest.mark.gpu
@@ -188,11 +189,6 @@ def test_special_rows_gradients_match_composition(cuda):
 
 
 # --------------------------------------------------------------------------------------------- determinism
-def same_bits(x, y):
-    it = {4: np.int32, 8: np.int64}[x.dtype.itemsize]
-    return x.shape == y.shape and np.array_equal(np.ascontiguousarray(x).view(it), np.ascontiguousarray(y).view(it))
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("det_mode", [False, True])
 def test_bitwise_reproducible_and_rows_independent(cuda, dtype, det_mode):

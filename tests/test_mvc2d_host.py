@@ -76,6 +76,13 @@ def test_workspace_query_and_argument_checks_are_host_only():
         assert bwd(*none9, 0, 4, 4, None, 0, None) == 0
         assert bwd(*none9, 2, 0, 0, None, 0, None) == 0
         assert bwd(*none9, 1, 4, 4, None, 0, None) != 0
+    # an N whose tile count would overflow an int: refused before any arithmetic on it
+    big = 2 ** 31 - 1
+    assert L.pp_mvc2d_workspace_bytes(1, big, 10, 4) == 0
+    for fwd in (L.pp_mvc2d_forward_f32, L.pp_mvc2d_forward_f64):
+        assert fwd(*none6, 1, big, 4, None) != 0
+    for bwd in (L.pp_mvc2d_backward_f32, L.pp_mvc2d_backward_f64):
+        assert bwd(*none9, 1, big, 4, None, 0, None) != 0
 
 
 def row_error(got, ref):

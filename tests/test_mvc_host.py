@@ -55,6 +55,13 @@ def test_workspace_query_and_argument_checks_are_host_only():
     assert L.pp_mvc3d_forward_f64(None, None, None, -1, None, None, None, None, 1, 1, 4, 4, None) != 0
     assert L.pp_mvc3d_backward_f32(None, None, None, 0, None, None, None, None, None, None, None, 1, 4, 4, 4, None, 0,
                                    None) != 0
+    # a P whose tile count would overflow an int: refused before any arithmetic on it
+    big = 2 ** 31 - 1
+    assert L.pp_mvc3d_workspace_bytes(1, big, 10, 4) == 0
+    for fwd in (L.pp_mvc3d_forward_f32, L.pp_mvc3d_forward_f64):
+        assert fwd(None, None, None, 0, None, None, None, None, 1, big, 4, 4, None) != 0
+    for bwd in (L.pp_mvc3d_backward_f32, L.pp_mvc3d_backward_f64):
+        assert bwd(None, None, None, 0, None, None, None, None, None, None, None, 1, big, 4, 4, None, 0, None) != 0
 
 
 def row_error(got, ref, shape):
