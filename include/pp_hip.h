@@ -642,6 +642,43 @@ int pp_mesh_vertex_normals_backward_f32(const float* vertices, const int* start,
                                         float* scratch, float* grad_vertices, int B, int N, int F, int weighting,
                                         int shared_topology, void* stream);
 
+/* ---- mesh surface sampling -------------------------------------------------------------------
+ * Area-weighted samples on a triangle mesh's surface and their re-evaluation on a deformed mesh; contract in DESIGN.md
+ * "Mesh surface sampling".  fp32 vertices (B,N,3); faces (Bt,F,3) int64 and start, nbr, codes as in "mesh normals";
+ * shared_topology != 0: they have one batch element, read by every b.  Every entry returns PP_EINVAL where B*N, B*F,
+ * B*S or 3F exceeds 2^31 - 1 or a size is negative, before any launch, and PP_OK without a launch where a size it works
+ * on is 0.
+ * pp_mesh_sample_cdf_f32: cdf (B,F) fp64 = the inclusive prefix sum of the fp32 areas (B,F) in fp64, one workgroup per
+ *   batch element with a fixed association: the same bytes on every run.
+ * pp_mesh_sample_forward_f32: one launch, one lane per sample, in one of two forms.  cdf != NULL: u holds u_stride
+ *   floats per sample, (u1) or (u1,u2,u3); target = double(u1) * cdf[b,F-1], face = the first f with cdf[b,f] > target,
+ *   su = sqrtf(u2), bary = (1 - su, su * (1 - u3), su * u3); where cdf[b,F-1] is not a positive finite number (or no f
+ *   is beyond target) face = -1 and bary is NaN; face_out (B,S) int64 and bary_out (B,S,3) receive them (either may be
+ *   NULL; u_stride == 1 serves face_out alone, points == NULL).  cdf == NULL: face_in (B,S) int64 and bary_in (B,S,3)
+ *   are the caller's.  points (B,S,3), d = 0..2: (w0*p0_d + w1*p1_d) + w2*p2_d with p_k = vertices[b, faces[face,k]],
+ *   every operation rounded on its own.  normals (B,S,3), with face_normals (B,F,3), both or neither NULL:
+ *   face_normals[b,face].  A face outside [0,F) and a vertex index outside [0,N) are only compared: points and normals
+ *   of that sample are NaN.
+ * pp_mesh_sample_backward_f32: grad_vertices (B,N,3), overwritten, from grad_points and grad_normals (B,S,3; one of
+ *   them may be NULL).  Builds the face -> sample lists of (face, B, F, S) in `workspace` (at least
+ *   pp_mesh_edges_workspace_bytes(B, F, S) bytes), sorted; per face gC[c] = sum over its samples in ascending order of
+ *   bary[c] * grad_points and gN = sum of grad_normals, plain fp32 additions from +0 by one lane, and for a list of
+ *   more than 256 samples by a workgroup of 512 lanes: lane t adds the entries t, t+512, ... in order, then a fixed
+ *   tree over the lanes of a wave and the waves in order; per vertex the sum of gC over its corner slice in slot order,
+ *   plus pp_mesh_face_normals_backward_f32's result for gN.  scratch: fp32, 9*B*F floats, and with grad_normals
+ *   3*B*F + 3*B*N more; the caller's, not grad_vertices.  A sample with face outside [0,F) and a face with a vertex
+ *   index outside [0,N) add nothing; a slot code >= 3F gives NaN.  No floating-point atomics: identical on every run. */
+int pp_mesh_sample_cdf_f32(const float* areas, double* cdf, int B, int F, void* stream);
+int pp_mesh_sample_forward_f32(const float* vertices, const long long* faces, const double* cdf, const float* u,
+                               int u_stride, const long long* face_in, const float* bary_in, const float* face_normals,
+                               long long* face_out, float* bary_out, float* points, float* normals, int B, int N, int F,
+                               int S, int shared_topology, void* stream);
+int pp_mesh_sample_backward_f32(const float* vertices, const long long* faces, const int* start, const int* nbr,
+                                const unsigned* codes, const long long* face, const float* bary,
+                                const float* grad_points, const float* grad_normals, float* scratch,
+                                float* grad_vertices, int B, int N, int F, int S, int shared_topology, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 
