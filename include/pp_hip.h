@@ -679,6 +679,49 @@ int pp_mesh_sample_backward_f32(const float* vertices, const long long* faces, c
                                 float* grad_vertices, int B, int N, int F, int S, int shared_topology, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ---- point-to-mesh distances -----------------------------------------------------------------
+ * The exact squared distance between a cloud and a triangle mesh, every (point, triangle) pair walked; contract in
+ * DESIGN.md "Point-to-mesh distances".  fp32 points (B,P,3) and vertices (B,N,3); faces (Bt,F,3) int64;
+ * shared_topology != 0: faces have one batch element, read by every b.  Every entry returns PP_EINVAL where B*N, B*F,
+ * B*P or 3F exceeds 2^31 - 1 or a size is negative, before any launch, and PP_OK without a launch where a size it works
+ * on is 0.
+ * The pair function of point p and triangle (a,b,c), fp32 with every operation rounded on its own, dot(u,v) =
+ *   (ux*vx + uy*vy) + uz*vz: ab = b-a, ac = c-a, ap = p-a, bp = p-b, cp = p-c, d1 = ab.ap, d2 = ac.ap, d3 = ab.bp,
+ *   d4 = ac.bp, d5 = ab.cp, d6 = ac.cp, vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4.  The first of
+ *   these that holds gives the weights: (1) d1 <= 0 and d2 <= 0: (1,0,0); (2) d3 >= 0 and d4 <= d3: (0,1,0);
+ *   (3) vc <= 0, d1 >= 0, d3 <= 0: t = d1/(d1-d3), (1-t,t,0); (4) d6 >= 0 and d5 <= d6: (0,0,1); (5) vb <= 0, d2 >= 0,
+ *   d6 <= 0: t = d2/(d2-d6), (1-t,0,t); (6) va <= 0, d4-d3 >= 0, d5-d6 >= 0: t = (d4-d3)/((d4-d3)+(d5-d6)), (0,1-t,t);
+ *   (7) t = 1/((va+vb)+vc), v = vb*t, w = vc*t, ((1-v)-w, v, w).  q_d = (w0*a_d + w1*b_d) + w2*c_d, r = p - q,
+ *   d = (rx*rx + ry*ry) + rz*rz.
+ * pp_mesh_distance_records_f32: records (B,F,16) fp32, 16-byte aligned: a, b, c, ab, ac of every face and a validity
+ *   word, 1 or, for a face with a vertex index outside [0,N) (only compared, never used as an address), 0.
+ * pp_mesh_point_face_forward_f32: one lane per point: from best = +inf, face = -1 the pairs f = 0, 1, ... in order, one
+ *   taken where d < best (the lowest face among equal distances; never a NaN; never a face whose validity word is 0).
+ *   dist (B,P), face (B,P) int64, bary (B,P,3) the weights of the pair taken; face = -1 leaves dist and bary NaN.
+ * pp_mesh_face_point_forward_f32: the same with the roles exchanged, one lane per face over the points i = 0, 1, ...:
+ *   dist (B,F), point (B,F) int64, bary (B,F,3).
+ * pp_mesh_distance_backward_f32: one lane per item, the items being the points (item_point == NULL: item s is point s
+ *   with the face item_face[b,s]) or the faces (item_face == NULL: item s is face s with the point item_point[b,s]);
+ *   exactly one of the two is NULL.  With q interpolated again from bary (B,S,3) and r = p - q: vec (B,S,3) =
+ *   (2*grad_dist) * r, neg (B,S,3) = -vec, face_out (B,S) int64 = the item's face; each of the three may be NULL, not
+ *   both vec and neg.  An item whose face is outside [0,F), whose point is outside [0,P) or whose face holds a vertex
+ *   index outside [0,N) gives +0 and face_out = -1.  grad_points (B,P,3), with item_point only, not vec: builds the
+ *   point -> face lists in `workspace` (at least pp_mesh_edges_workspace_bytes(B, P, F) bytes), sorted, and per point
+ *   adds vec over its faces in ascending order, plain fp32 additions from +0.  The vertices' gradient is
+ *   pp_mesh_sample_backward_f32's for (face or face_out, bary, grad_points = neg).  No floating-point atomics:
+ *   identical on every run. */
+int pp_mesh_distance_records_f32(const float* vertices, const long long* faces, float* records, int B, int N, int F,
+                                 int shared_topology, void* stream);
+int pp_mesh_point_face_forward_f32(const float* points, const float* records, float* dist, long long* face,
+                                   float* bary, int B, int P, int F, void* stream);
+int pp_mesh_face_point_forward_f32(const float* points, const float* records, float* dist, long long* point,
+                                   float* bary, int B, int P, int F, void* stream);
+int pp_mesh_distance_backward_f32(const float* points, const float* vertices, const long long* faces,
+                                  const long long* item_face, const long long* item_point, const float* bary,
+                                  const float* grad_dist, float* vec, float* neg, long long* face_out,
+                                  float* grad_points, int B, int N, int F, int P, int shared_topology, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -129,6 +129,10 @@ SIGNATURES = {
     "pp_mesh_sample_cdf_f32": [_P, _P, _I, _I, _P],
     "pp_mesh_sample_forward_f32": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "pp_mesh_sample_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_mesh_distance_records_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "pp_mesh_point_face_forward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "pp_mesh_face_point_forward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "pp_mesh_distance_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
 }
 _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_bytes": _c_size_t,
              "pp_nmdistance_forward_workspace_bytes": _c_size_t,

@@ -1,0 +1,377 @@
+// mesh_distance.hip -- the exact squared distance between a point cloud and a triangle mesh, in both directions, by
+// walking every (point, triangle) pair.  The seventh mesh operator; contract in DESIGN.md "Point-to-mesh distances".
+//
+//   records      one lane per (b, face): the face's corners a, b, c, its edges ab = b - a and ac = c - a and a validity
+//                word, 16 floats, so that the pair loops gather nothing and check no index
+//   point->face  one lane per point, a workgroup within one batch element; the records come through LDS in tiles of
+//                kPdFaceTile, in ascending order; the record of a step is the same for every lane (an LDS broadcast)
+//   face->point  one lane per face with its record in registers; the points of the batch element come through LDS in
+//                tiles of kPdPointTile, in ascending order
+//   Both keep (best, index, weights) from (+inf, -1, NaN) and take a pair where d < best: the lowest index among equal
+//   distances, never a NaN, never a face with a vertex index outside [0, N).
+//   backward     one lane per item: r = p - q with q interpolated again, (2 g) r and its negative; for face->point the
+//                point -> face lists of the call (pp::bucket_build: buckets the B*P points, items the faces, sorted) and
+//                per point the sum of its faces' vectors in ascending order.  The vertices' gradient is
+//                pp_mesh_sample_backward_f32's on the negated vectors.
+//
+// pd_pair is the one pair function: Ericson's region walk with every operation rounded on its own, in the operation
+// order of mesh_distance.distance_composition, which it equals to the bit.
+//
+// No floating-point atomics: every output word is written once and the bits are the same on every run.  An index of
+// `faces` outside [0, N), and in the backward a face outside [0, F) or a point outside [0, P), are only compared,
+// never used as an address.
+#include "mesh_common.h"   // pp::V3, md_load, md_sub; pp::blocks, pp::quiet_nan; bucket_lists.h
+
+namespace {
+
+using pp::V3;
+using pp::md_load;
+using pp::md_sub;
+
+constexpr int kPdThreads = 256;
+constexpr int kPdRecord = 16;         // floats of a face record: a, b, c, ab, ac, valid
+constexpr int kPdFaceTile = 256;      // records in LDS: 16 KB
+constexpr int kPdPointTile = 1024;    // points in LDS: 12 KB
+
+struct PdTri {
+  V3 a, b, c, ab, ac;
+};
+struct PdPair {
+  float d, w0, w1, w2;
+};
+
+// (ux vx + uy vy) + uz vz, three products and two sums
+__device__ __forceinline__ float pd_dot(V3 u, V3 v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
+
+// the closest point of triangle t to p as weights of (a, b, c), and the squared distance to it.  The regions are
+// tried in the contract's order; each needs at most one division, so one is made, of the operands of the first
+// region that holds among those that divide.
+__device__ __forceinline__ PdPair pd_pair(V3 p, const PdTri& t) {
+  const V3 ap = md_sub(p, t.a), bp = md_sub(p, t.b), cp = md_sub(p, t.c);
+  const float d1 = pd_dot(t.ab, ap), d2 = pd_dot(t.ac, ap);
+  const float d3 = pd_dot(t.ab, bp), d4 = pd_dot(t.ac, bp);
+  const float d5 = pd_dot(t.ab, cp), d6 = pd_dot(t.ac, cp);
+  const float vc = d1 * d4 - d3 * d2;
+  const float vb = d5 * d2 - d1 * d6;
+  const float va = d3 * d6 - d5 * d4;
+  const float e43 = d4 - d3, e56 = d5 - d6;
+  const bool r1 = d1 <= 0.0f && d2 <= 0.0f;
+  const bool r2 = d3 >= 0.0f && d4 <= d3;
+  const bool r3 = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+  const bool r4 = d6 >= 0.0f && d5 <= d6;
+  const bool r5 = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+  const bool r6 = va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f;
+  const float num = r3 ? d1 : r5 ? d2 : r6 ? e43 : 1.0f;
+  const float den = r3 ? d1 - d3 : r5 ? d2 - d6 : r6 ? e43 + e56 : (va + vb) + vc;
+  const float q = num / den;
+  const float omq = 1.0f - q;
+  const float v7 = vb * q, w7 = vc * q;
+  const float u7 = (1.0f - v7) - w7;
+  PdPair r;
+  r.w0 = r1 ? 1.0f : r2 ? 0.0f : r3 ? omq : r4 ? 0.0f : r5 ? omq : r6 ? 0.0f : u7;
+  r.w1 = r1 ? 0.0f : r2 ? 1.0f : r3 ? q : r4 ? 0.0f : r5 ? 0.0f : r6 ? omq : v7;
+  r.w2 = r1 ? 0.0f : r2 ? 0.0f : r3 ? 0.0f : r4 ? 1.0f : r5 ? q : r6 ? q : w7;
+  const float rx = p.x - ((r.w0 * t.a.x + r.w1 * t.b.x) + r.w2 * t.c.x);
+  const float ry = p.y - ((r.w0 * t.a.y + r.w1 * t.b.y) + r.w2 * t.c.y);
+  const float rz = p.z - ((r.w0 * t.a.z + r.w1 * t.b.z) + r.w2 * t.c.z);
+  r.d = (rx * rx + ry * ry) + rz * rz;
+  return r;
+}
+
+// the record as four float4 words, and back; w3.w is the validity word
+__device__ __forceinline__ PdTri pd_unpack(float4 w0, float4 w1, float4 w2, float4 w3) {
+  PdTri t;
+  t.a = {w0.x, w0.y, w0.z};
+  t.b = {w0.w, w1.x, w1.y};
+  t.c = {w1.z, w1.w, w2.x};
+  t.ab = {w2.y, w2.z, w2.w};
+  t.ac = {w3.x, w3.y, w3.z};
+  return t;
+}
+
+// ---- records --------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kPdThreads) void pd_records_kernel(const float* __restrict__ vertices,
+                                                                const long long* __restrict__ faces,
+                                                                float4* __restrict__ records, long long rows, int N,
+                                                                int F, int shared) {
+  const long long x = (long long)blockIdx.x * kPdThreads + threadIdx.x;
+  if (x >= rows) return;
+  const long long b = x / F;
+  const long long* __restrict__ row = faces + (shared ? x - b * F : x) * 3;
+  const long long i0 = row[0], i1 = row[1], i2 = row[2];
+  float4 w0 = {0.0f, 0.0f, 0.0f, 0.0f}, w1 = w0, w2 = w0, w3 = w0;
+  if (!(i0 < 0 || i0 >= N || i1 < 0 || i1 >= N || i2 < 0 || i2 >= N)) {
+    const float* __restrict__ vb = vertices + (size_t)b * N * 3;
+    const V3 a = md_load(vb, i0), c1 = md_load(vb, i1), c2 = md_load(vb, i2);
+    const V3 ab = md_sub(c1, a), ac = md_sub(c2, a);
+    w0 = {a.x, a.y, a.z, c1.x};
+    w1 = {c1.y, c1.z, c2.x, c2.y};
+    w2 = {c2.z, ab.x, ab.y, ab.z};
+    w3 = {ac.x, ac.y, ac.z, 1.0f};
+  }
+  float4* __restrict__ out = records + (size_t)x * (kPdRecord / 4);
+  out[0] = w0;
+  out[1] = w1;
+  out[2] = w2;
+  out[3] = w3;
+}
+
+// ---- forward --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pd_store(float* __restrict__ dist, long long* __restrict__ index,
+                                         float* __restrict__ bary, size_t x, float best, int arg, float w0, float w1,
+                                         float w2) {
+  dist[x] = arg < 0 ? pp::quiet_nan() : best;
+  index[x] = arg;
+  bary[x * 3] = w0;
+  bary[x * 3 + 1] = w1;
+  bary[x * 3 + 2] = w2;
+}
+
+__global__ __launch_bounds__(kPdThreads) void pd_point_face_kernel(const float* __restrict__ points,
+                                                                   const float4* __restrict__ records,
+                                                                   float* __restrict__ dist,
+                                                                   long long* __restrict__ face,
+                                                                   float* __restrict__ bary, int P, int F,
+                                                                   int blocks_per_element) {
+  __shared__ float4 s_rec[kPdFaceTile * (kPdRecord / 4)];
+  const int t = threadIdx.x;
+  const long long b = blockIdx.x / blocks_per_element;
+  const long long i = (long long)(blockIdx.x - (unsigned)b * blocks_per_element) * kPdThreads + t;
+  const bool live = i < P;
+  V3 p = {0.0f, 0.0f, 0.0f};
+  if (live) p = md_load(points + (size_t)b * P * 3, i);
+  const float4* __restrict__ rb = records + (size_t)b * F * (kPdRecord / 4);
+  float best = __builtin_inff();
+  int arg = -1;
+  float w0 = pp::quiet_nan(), w1 = w0, w2 = w0;
+  for (int f0 = 0; f0 < F; f0 += kPdFaceTile) {
+    const int n = F - f0 < kPdFaceTile ? F - f0 : kPdFaceTile;
+    __syncthreads();   // the previous tile's readers are done
+    for (int k = t; k < n * (kPdRecord / 4); k += kPdThreads) s_rec[k] = rb[(size_t)f0 * (kPdRecord / 4) + k];
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+      const float4 q3 = s_rec[j * 4 + 3];
+      if (q3.w == 0.0f) continue;   // (the whole workgroup) a face with a vertex index out of range
+      const PdTri tri = pd_unpack(s_rec[j * 4], s_rec[j * 4 + 1], s_rec[j * 4 + 2], q3);
+      const PdPair r = pd_pair(p, tri);
+      if (r.d < best) {
+        best = r.d;
+        arg = f0 + j;
+        w0 = r.w0, w1 = r.w1, w2 = r.w2;
+      }
+    }
+  }
+  if (live) pd_store(dist, face, bary, (size_t)b * P + i, best, arg, w0, w1, w2);
+}
+
+__global__ __launch_bounds__(kPdThreads) void pd_face_point_kernel(const float* __restrict__ points,
+                                                                   const float4* __restrict__ records,
+                                                                   float* __restrict__ dist,
+                                                                   long long* __restrict__ point,
+                                                                   float* __restrict__ bary, int P, int F,
+                                                                   int blocks_per_element) {
+  __shared__ float s_pt[kPdPointTile * 3];
+  const int t = threadIdx.x;
+  const long long b = blockIdx.x / blocks_per_element;
+  const long long f = (long long)(blockIdx.x - (unsigned)b * blocks_per_element) * kPdThreads + t;
+  const bool live = f < F;
+  float4 q0 = {0.0f, 0.0f, 0.0f, 0.0f}, q1 = q0, q2 = q0, q3 = q0;
+  if (live) {
+    const float4* __restrict__ rec = records + ((size_t)b * F + f) * (kPdRecord / 4);
+    q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
+  }
+  const PdTri tri = pd_unpack(q0, q1, q2, q3);
+  const bool valid = q3.w != 0.0f;
+  const float* __restrict__ pb = points + (size_t)b * P * 3;
+  float best = __builtin_inff();
+  int arg = -1;
+  float w0 = pp::quiet_nan(), w1 = w0, w2 = w0;
+  for (int p0 = 0; p0 < P; p0 += kPdPointTile) {
+    const int n = P - p0 < kPdPointTile ? P - p0 : kPdPointTile;
+    __syncthreads();   // the previous tile's readers are done
+    for (int k = t; k < n * 3; k += kPdThreads) s_pt[k] = pb[(size_t)p0 * 3 + k];
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+      const V3 p = {s_pt[j * 3], s_pt[j * 3 + 1], s_pt[j * 3 + 2]};
+      const PdPair r = pd_pair(p, tri);
+      if (valid && r.d < best) {
+        best = r.d;
+        arg = p0 + j;
+        w0 = r.w0, w1 = r.w1, w2 = r.w2;
+      }
+    }
+  }
+  if (live) pd_store(dist, point, bary, (size_t)b * F + f, best, arg, w0, w1, w2);
+}
+
+// ---- backward -------------------------------------------------------------------------------------------------------
+// Item s of batch element b pairs the face item_face[b,s] (NULL: s) with the point item_point[b,s] (NULL: s) at the
+// weights bary[b,s]: vec = (2 g) (p - q), neg = -vec, face_out = the face, each may be NULL.  An item whose face or
+// point is out of range, or whose face holds a vertex index out of range, gives +0 and face_out = -1.
+__global__ __launch_bounds__(kPdThreads) void pd_backward_kernel(
+    const float* __restrict__ points, const float* __restrict__ vertices, const long long* __restrict__ faces,
+    const long long* __restrict__ item_face, const long long* __restrict__ item_point, const float* __restrict__ bary,
+    const float* __restrict__ g, float* __restrict__ vec, float* __restrict__ neg, long long* __restrict__ face_out,
+    long long total, int N, int F, int P, int S, int shared) {
+  const long long x = (long long)blockIdx.x * kPdThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long b = x / S;
+  const long long f = item_face ? item_face[x] : x - b * S;
+  const long long i = item_point ? item_point[x] : x - b * S;
+  bool ok = f >= 0 && f < F && i >= 0 && i < P;
+  long long i0 = 0, i1 = 0, i2 = 0;
+  if (ok) {
+    const long long* __restrict__ row = faces + ((shared ? 0 : b * F) + f) * 3;
+    i0 = row[0], i1 = row[1], i2 = row[2];
+    ok = !(i0 < 0 || i0 >= N || i1 < 0 || i1 >= N || i2 < 0 || i2 >= N);
+  }
+  V3 out = {0.0f, 0.0f, 0.0f}, opp = out;
+  if (ok) {
+    const float* __restrict__ vb = vertices + (size_t)b * N * 3;
+    const V3 a = md_load(vb, i0), c1 = md_load(vb, i1), c2 = md_load(vb, i2);
+    const V3 p = md_load(points + (size_t)b * P * 3, i);
+    const float w0 = bary[x * 3], w1 = bary[x * 3 + 1], w2 = bary[x * 3 + 2];
+    const float rx = p.x - ((w0 * a.x + w1 * c1.x) + w2 * c2.x);
+    const float ry = p.y - ((w0 * a.y + w1 * c1.y) + w2 * c2.y);
+    const float rz = p.z - ((w0 * a.z + w1 * c1.z) + w2 * c2.z);
+    const float s2 = 2.0f * g[x];
+    out = {s2 * rx, s2 * ry, s2 * rz};
+    opp = {-out.x, -out.y, -out.z};
+  }
+  if (vec) {
+    vec[x * 3] = out.x;
+    vec[x * 3 + 1] = out.y;
+    vec[x * 3 + 2] = out.z;
+  }
+  if (neg) {
+    neg[x * 3] = opp.x;
+    neg[x * 3 + 1] = opp.y;
+    neg[x * 3 + 2] = opp.z;
+  }
+  if (face_out) face_out[x] = ok ? f : -1;
+}
+
+// FILL = false: the points' face counts; FILL = true: the lists.  A face whose point is out of range takes no part.
+template <bool FILL>
+__global__ __launch_bounds__(kPdThreads) void pd_lists_kernel(const long long* __restrict__ point,
+                                                              unsigned* __restrict__ cursor,
+                                                              unsigned* __restrict__ entries, long long total, int F,
+                                                              int P) {
+  const long long x = (long long)blockIdx.x * kPdThreads + threadIdx.x;
+  if (x >= total) return;
+  const long long i = point[x];
+  if (i < 0 || i >= P) return;
+  const long long b = x / F;
+  pp::bucket_put<FILL>(cursor, entries, b, P, (long long)F, (size_t)i, (unsigned)(x - b * F));
+}
+
+// one lane per (b, point): the sum of vec over the point's sorted face list, plain fp32 additions from +0
+__global__ __launch_bounds__(kPdThreads) void pd_point_sums_kernel(const unsigned* __restrict__ start,
+                                                                   const unsigned* __restrict__ cursor,
+                                                                   const unsigned* __restrict__ entries,
+                                                                   const float* __restrict__ vec,
+                                                                   float* __restrict__ grad_points, long long rows,
+                                                                   int F, int P) {
+  const long long i = (long long)blockIdx.x * kPdThreads + threadIdx.x;
+  if (i >= rows) return;
+  const long long b = i / P;
+  const unsigned s0 = start[i], n = cursor[i] - s0;
+  const unsigned* __restrict__ list = entries + (size_t)b * F + s0;
+  const float* __restrict__ vb = vec + (size_t)b * F * 3;
+  V3 acc = {0.0f, 0.0f, 0.0f};
+  for (unsigned q = 0; q < n; ++q) {
+    const unsigned e = list[q];
+    V3 term = {pp::quiet_nan(), pp::quiet_nan(), pp::quiet_nan()};
+    if (e < (unsigned)F) term = md_load(vb, e);
+    acc = {acc.x + term.x, acc.y + term.y, acc.z + term.z};
+  }
+  grad_points[i * 3] = acc.x;
+  grad_points[i * 3 + 1] = acc.y;
+  grad_points[i * 3 + 2] = acc.z;
+}
+
+// the sizes every entry checks: the rows of a launch and the slot codes fit 31 bits
+bool pd_sizes_ok(int B, int N, int F, int P) {
+  return B >= 0 && N >= 0 && F >= 0 && P >= 0 && (long long)B * N <= 0x7fffffffLL && (long long)B * F <= 0x7fffffffLL &&
+         (long long)B * P <= 0x7fffffffLL && 3LL * F <= 0x7fffffffLL;
+}
+
+}  // namespace
+
+extern "C" int pp_mesh_distance_records_f32(const float* vertices, const long long* faces, float* records, int B, int N,
+                                            int F, int shared_topology, void* stream) {
+  if (!pd_sizes_ok(B, N, F, 0)) return PP_EINVAL;
+  if (B == 0 || N == 0 || F == 0) return PP_OK;
+  if (!vertices || !faces || !records || ((uintptr_t)records & 15u)) return PP_EINVAL;
+  const long long rows = (long long)B * F;
+  pd_records_kernel<<<dim3(pp::blocks(rows, kPdThreads)), dim3(kPdThreads), 0, (hipStream_t)stream>>>(
+      vertices, faces, reinterpret_cast<float4*>(records), rows, N, F, shared_topology != 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_point_face_forward_f32(const float* points, const float* records, float* dist, long long* face,
+                                              float* bary, int B, int P, int F, void* stream) {
+  if (!pd_sizes_ok(B, 0, F, P)) return PP_EINVAL;
+  if (B == 0 || P == 0 || F == 0) return PP_OK;
+  if (!points || !records || !dist || !face || !bary || ((uintptr_t)records & 15u)) return PP_EINVAL;
+  const int per_element = (int)pp::blocks(P, kPdThreads);
+  if ((long long)B * per_element > 0x7fffffffLL) return PP_EINVAL;
+  pd_point_face_kernel<<<dim3((unsigned)(B * per_element)), dim3(kPdThreads), 0, (hipStream_t)stream>>>(
+      points, reinterpret_cast<const float4*>(records), dist, face, bary, P, F, per_element);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_face_point_forward_f32(const float* points, const float* records, float* dist, long long* point,
+                                              float* bary, int B, int P, int F, void* stream) {
+  if (!pd_sizes_ok(B, 0, F, P)) return PP_EINVAL;
+  if (B == 0 || P == 0 || F == 0) return PP_OK;
+  if (!points || !records || !dist || !point || !bary || ((uintptr_t)records & 15u)) return PP_EINVAL;
+  const int per_element = (int)pp::blocks(F, kPdThreads);
+  if ((long long)B * per_element > 0x7fffffffLL) return PP_EINVAL;
+  pd_face_point_kernel<<<dim3((unsigned)(B * per_element)), dim3(kPdThreads), 0, (hipStream_t)stream>>>(
+      points, reinterpret_cast<const float4*>(records), dist, point, bary, P, F, per_element);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+extern "C" int pp_mesh_distance_backward_f32(const float* points, const float* vertices, const long long* faces,
+                                             const long long* item_face, const long long* item_point,
+                                             const float* bary, const float* grad_dist, float* vec, float* neg,
+                                             long long* face_out, float* grad_points, int B, int N, int F, int P,
+                                             int shared_topology, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+  if (!pd_sizes_ok(B, N, F, P)) return PP_EINVAL;
+  if (B == 0 || N == 0 || F == 0 || P == 0) return PP_OK;
+  if (!points || !vertices || !faces || !bary || !grad_dist || (item_face != nullptr) == (item_point != nullptr))
+    return PP_EINVAL;
+  if (grad_points && (!item_point || !vec || vec == grad_points)) return PP_EINVAL;
+  if (!vec && !neg) return PP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int S = item_face ? P : F;   // one item per point, or one per face
+  const long long total = (long long)B * S;
+  pd_backward_kernel<<<dim3(pp::blocks(total, kPdThreads)), dim3(kPdThreads), 0, s>>>(
+      points, vertices, faces, item_face, item_point, bary, grad_dist, vec, neg, face_out, total, N, F, P, S,
+      shared_topology != 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  if (!grad_points) return PP_OK;
+  const pp::BucketLayout L = pp::bucket_layout(B, P, F, false);
+  unsigned char* ws = (unsigned char*)workspace;
+  if (!ws || workspace_bytes < L.total) return PP_EINVAL;
+  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
+  unsigned* entries = reinterpret_cast<unsigned*>(ws + L.entries);
+  const int rc = pp::bucket_build(ws, L, entries, nullptr, B, P, F, true, s, [&](bool fill) {
+    const dim3 grid(pp::blocks(total, kPdThreads)), block(kPdThreads);
+    if (fill)
+      pd_lists_kernel<true><<<grid, block, 0, s>>>(item_point, cursor, entries, total, F, P);
+    else
+      pd_lists_kernel<false><<<grid, block, 0, s>>>(item_point, cursor, entries, total, F, P);
+  });
+  if (rc != PP_OK) return rc;
+  const long long rows = (long long)B * P;
+  pd_point_sums_kernel<<<dim3(pp::blocks(rows, kPdThreads)), dim3(kPdThreads), 0, s>>>(
+      reinterpret_cast<const unsigned*>(ws + L.start), cursor, entries, vec, grad_points, rows, F, P);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}

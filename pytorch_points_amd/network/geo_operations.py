@@ -10,7 +10,8 @@ the mesh edge utilities edge_vertex_indices and get_edge_lengths (:562-600), and
 get_edge_points (utils/geometry_utils.py:242-341: build_gemm, get_edge_points, get_side_points), and the mesh normals
 mesh_face_normals / mesh_vertex_normals (the reference has no vertex normals) with normalize_to_same_area
 (utils/geometry_utils.py:15-25), and the step from a mesh to points on its surface, which the reference lacks:
-mesh_sample_faces, mesh_interpolate and sample_points_from_meshes of pytorch_points_amd.mesh_sample under their names.
+mesh_sample_faces, mesh_interpolate and sample_points_from_meshes of pytorch_points_amd.mesh_sample under their names,
+and the exact distances point_face_distance and face_point_distance of pytorch_points_amd.mesh_distance.
 Every function of the reference's geo_operations.py is served."""
 import collections
 
@@ -25,6 +26,7 @@ from .. import mesh_dihedral as _mesh_dihedral
 from .. import mesh_edges as _mesh_edges
 from .. import mesh_laplacian as _mesh_laplacian
 from .. import mesh_normals as _mesh_normals
+from ..mesh_distance import face_point_distance, point_face_distance  # noqa: F401 (no counterpart in the reference)
 from ..mesh_sample import mesh_interpolate, mesh_sample_faces, sample_points_from_meshes  # noqa: F401  (no counterpart)
 from .. import mvc as _mvc
 from .. import mvc2d as _mvc2d
