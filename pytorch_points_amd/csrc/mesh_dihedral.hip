@@ -27,7 +27,7 @@
 //
 // An index outside [0, n_vertices) is never used as an address: the builds compare it and leave out what it belongs
 // to, the forward writes NaN for such an edge and the backward adds NaN for it.
-#include "mesh_common.h"   // pp::mesh_half_edge, pp::mesh_build_ok, the three-vectors; pp::blocks, pp::quiet_nan
+#include "mesh_common.h"   // pp::mesh_half_edge, mesh_build_ok, mesh_row, V3 and v3_*; pp::blocks, pp::quiet_nan
 
 namespace {
 
@@ -115,11 +115,7 @@ __global__ __launch_bounds__(kMdThreads) void md_decode_kernel(const long long* 
 }
 
 // ---- the chain ----------------------------------------------------------------------------------------------------
-using pp::V3;   // mesh_common.h: md_load, md_sub, md_dop (Kahan's difference of products), md_cross, md_dot
-using pp::md_cross;
-using pp::md_dot;
-using pp::md_load;
-using pp::md_sub;
+using namespace pp;   // mesh_common.h: V3 and v3_*; every dot product of the chain is v3_dot_fused
 
 // a row in canonical order (ends ascending, wings ascending) and what became of the caller's slots
 struct MdRow {
@@ -146,19 +142,18 @@ struct MdChain {
   float la, lb, d_raw;  // |na|, |nb|, the dot before the clamp
 };
 __device__ __forceinline__ MdChain md_chain(const float* __restrict__ vb, const MdRow& r) {
-  const V3 p0 = md_load(vb, r.i0), p1 = md_load(vb, r.i1), p2 = md_load(vb, r.i2), p3 = md_load(vb, r.i3);
+  const V3 p0 = v3_load(vb, r.i0), p1 = v3_load(vb, r.i1), p2 = v3_load(vb, r.i2), p3 = v3_load(vb, r.i3);
   MdChain c;
-  c.u = md_sub(p1, p0);
-  c.w = md_sub(p2, p0);
-  c.s = md_sub(p3, p1);
-  c.t = md_sub(p0, p1);
-  const V3 na = md_cross(c.w, c.u), nb = md_cross(c.s, c.t);
-  c.la = sqrtf(md_dot(na, na));
-  c.lb = sqrtf(md_dot(nb, nb));
-  const float da = c.la > kMdEps ? c.la : kMdEps, db = c.lb > kMdEps ? c.lb : kMdEps;
-  c.ua = {na.x / da, na.y / da, na.z / da};
-  c.ub = {nb.x / db, nb.y / db, nb.z / db};
-  c.d_raw = md_dot(c.ua, c.ub);
+  c.u = v3_sub(p1, p0);
+  c.w = v3_sub(p2, p0);
+  c.s = v3_sub(p3, p1);
+  c.t = v3_sub(p0, p1);
+  const V3 na = v3_cross(c.w, c.u), nb = v3_cross(c.s, c.t);
+  c.la = sqrtf(v3_dot_fused(na, na));
+  c.lb = sqrtf(v3_dot_fused(nb, nb));
+  c.ua = v3_div(na, c.la > kMdEps ? c.la : kMdEps);
+  c.ub = v3_div(nb, c.lb > kMdEps ? c.lb : kMdEps);
+  c.d_raw = v3_dot_fused(c.ua, c.ub);
   return c;
 }
 __device__ __forceinline__ float md_clamp(float d) {
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(kMdThreads) void md_forward_kernel(const float* __r
   }
   const MdRow r = md_row(edge_points + (tb * Ecap + e) * 4, N);
   if (!r.in_range) {
-    out[x] = pp::quiet_nan();
+    out[x] = quiet_nan();
     return;
   }
   const MdChain c = md_chain(vertices + (size_t)b * N * 3, r);
@@ -200,15 +195,13 @@ __global__ __launch_bounds__(kMdThreads) void md_backward_kernel(
     long long rows, int N, int Ecap, int shared) {
   const long long i = (long long)blockIdx.x * kMdThreads + threadIdx.x;
   if (i >= rows) return;
-  const long long b = i / N;
-  const long long v = i - b * N;
-  const long long tb = shared ? 0 : b;
-  const float* __restrict__ vb = vertices + (size_t)b * N * 3;
-  const long long* __restrict__ eb = edge_points + (size_t)tb * Ecap * 4;
-  const unsigned* __restrict__ list = inc_entries + (size_t)tb * Ecap * 4;
-  const float* __restrict__ gb_ = grad_out + (size_t)b * Ecap;
-  const int* __restrict__ st = inc_start + (size_t)tb * ((size_t)N + 1) + v;
-  float ax = 0.0f, ay = 0.0f, az = 0.0f;
+  const MeshRow w = mesh_row(i, N, shared);
+  const float* __restrict__ vb = vertices + (size_t)w.b * N * 3;
+  const long long* __restrict__ eb = edge_points + (size_t)w.tb * Ecap * 4;
+  const unsigned* __restrict__ list = inc_entries + (size_t)w.tb * Ecap * 4;
+  const float* __restrict__ gb_ = grad_out + (size_t)w.b * Ecap;
+  const int* __restrict__ st = inc_start + (size_t)w.tb * ((size_t)N + 1) + w.i;   // (read as it is, not clipped)
+  V3 acc = {0.0f, 0.0f, 0.0f};
   for (int q = st[0], q1 = st[1]; q < q1; ++q) {
     const unsigned code = list[q];
     const unsigned e = code >> 2;
@@ -217,7 +210,7 @@ __global__ __launch_bounds__(kMdThreads) void md_backward_kernel(
     const MdRow r = md_row(eb + (size_t)e * 4, N);
     V3 term;
     if (!r.in_range) {
-      term = {pp::quiet_nan(), pp::quiet_nan(), pp::quiet_nan()};
+      term = v3_nan();
     } else {
       if (slot < 2u ? r.swap01 : r.swap23) slot ^= 1u;   // the caller's slot in canonical order
       const MdChain c = md_chain(vb, r);
@@ -228,29 +221,19 @@ __global__ __launch_bounds__(kMdThreads) void md_backward_kernel(
         fa = g / c.la;
         fb = g / c.lb;
       }
-      const V3 ga = {fa * __builtin_fmaf(-d, c.ua.x, c.ub.x), fa * __builtin_fmaf(-d, c.ua.y, c.ub.y),
-                     fa * __builtin_fmaf(-d, c.ua.z, c.ub.z)};
-      const V3 gb = {fb * __builtin_fmaf(-d, c.ub.x, c.ua.x), fb * __builtin_fmaf(-d, c.ub.y, c.ua.y),
-                     fb * __builtin_fmaf(-d, c.ub.z, c.ua.z)};
+      const V3 ga = v3_scale(fa, v3_fma(-d, c.ua, c.ub)), gb = v3_scale(fb, v3_fma(-d, c.ub, c.ua));
       if (slot == 2u) {
-        term = md_cross(c.u, ga);
+        term = v3_cross(c.u, ga);
       } else if (slot == 3u) {
-        term = md_cross(c.t, gb);
+        term = v3_cross(c.t, gb);
       } else {
-        const V3 uga = md_cross(c.u, ga), gaw = md_cross(ga, c.w), tgb = md_cross(c.t, gb), gbs = md_cross(gb, c.s);
-        if (slot == 0u)
-          term = {gbs.x - (uga.x + gaw.x), gbs.y - (uga.y + gaw.y), gbs.z - (uga.z + gaw.z)};
-        else
-          term = {gaw.x - (tgb.x + gbs.x), gaw.y - (tgb.y + gbs.y), gaw.z - (tgb.z + gbs.z)};
+        const V3 uga = v3_cross(c.u, ga), gaw = v3_cross(ga, c.w), tgb = v3_cross(c.t, gb), gbs = v3_cross(gb, c.s);
+        term = slot == 0u ? v3_sub(gbs, v3_add(uga, gaw)) : v3_sub(gaw, v3_add(tgb, gbs));
       }
     }
-    ax = ax + term.x;
-    ay = ay + term.y;
-    az = az + term.z;
+    acc = v3_add(acc, term);
   }
-  grad[i * 3] = ax;
-  grad[i * 3 + 1] = ay;
-  grad[i * 3 + 2] = az;
+  v3_store(grad, i, acc);
 }
 
 }  // namespace

@@ -10,8 +10,8 @@
 //   Both keep (best, index, weights) from (+inf, -1, NaN) and take a pair where d < best: the lowest index among equal
 //   distances, never a NaN, never a face with a vertex index outside [0, N).
 //   backward     one lane per item: r = p - q with q interpolated again, (2 g) r and its negative; for face->point the
-//                point -> face lists of the call (pp::bucket_build: buckets the B*P points, items the faces, sorted) and
-//                per point the sum of its faces' vectors in ascending order.  The vertices' gradient is
+//                point -> face lists of the call (pp::mesh_item_lists: buckets the B*P points, items the faces,
+//                sorted) and per point the sum of its faces' vectors in ascending order.  The vertices' gradient is
 //                pp_mesh_sample_backward_f32's on the negated vectors.
 //
 // pd_pair is the one pair function: Ericson's region walk with every operation rounded on its own, in the operation
@@ -20,13 +20,11 @@
 // No floating-point atomics: every output word is written once and the bits are the same on every run.  An index of
 // `faces` outside [0, N), and in the backward a face outside [0, F) or a point outside [0, P), are only compared,
 // never used as an address.
-#include "mesh_common.h"   // pp::V3, md_load, md_sub; pp::blocks, pp::quiet_nan; bucket_lists.h
+#include "mesh_common.h"   // pp::mesh_face, mesh_item_lists, mesh_sizes_ok, V3 and v3_*; pp::blocks, pp::quiet_nan
 
 namespace {
 
-using pp::V3;
-using pp::md_load;
-using pp::md_sub;
+using namespace pp;   // mesh_common.h's rows, three-vectors and item lists; every dot product is v3_dot_rounded
 
 constexpr int kPdThreads = 256;
 constexpr int kPdRecord = 16;         // floats of a face record: a, b, c, ab, ac, valid
@@ -40,17 +38,14 @@ struct PdPair {
   float d, w0, w1, w2;
 };
 
-// (ux vx + uy vy) + uz vz, three products and two sums
-__device__ __forceinline__ float pd_dot(V3 u, V3 v) { return (u.x * v.x + u.y * v.y) + u.z * v.z; }
-
 // the closest point of triangle t to p as weights of (a, b, c), and the squared distance to it.  The regions are
 // tried in the contract's order; each needs at most one division, so one is made, of the operands of the first
 // region that holds among those that divide.
 __device__ __forceinline__ PdPair pd_pair(V3 p, const PdTri& t) {
-  const V3 ap = md_sub(p, t.a), bp = md_sub(p, t.b), cp = md_sub(p, t.c);
-  const float d1 = pd_dot(t.ab, ap), d2 = pd_dot(t.ac, ap);
-  const float d3 = pd_dot(t.ab, bp), d4 = pd_dot(t.ac, bp);
-  const float d5 = pd_dot(t.ab, cp), d6 = pd_dot(t.ac, cp);
+  const V3 ap = v3_sub(p, t.a), bp = v3_sub(p, t.b), cp = v3_sub(p, t.c);
+  const float d1 = v3_dot_rounded(t.ab, ap), d2 = v3_dot_rounded(t.ac, ap);
+  const float d3 = v3_dot_rounded(t.ab, bp), d4 = v3_dot_rounded(t.ac, bp);
+  const float d5 = v3_dot_rounded(t.ab, cp), d6 = v3_dot_rounded(t.ac, cp);
   const float vc = d1 * d4 - d3 * d2;
   const float vb = d5 * d2 - d1 * d6;
   const float va = d3 * d6 - d5 * d4;
@@ -71,10 +66,8 @@ __device__ __forceinline__ PdPair pd_pair(V3 p, const PdTri& t) {
   r.w0 = r1 ? 1.0f : r2 ? 0.0f : r3 ? omq : r4 ? 0.0f : r5 ? omq : r6 ? 0.0f : u7;
   r.w1 = r1 ? 0.0f : r2 ? 1.0f : r3 ? q : r4 ? 0.0f : r5 ? 0.0f : r6 ? omq : v7;
   r.w2 = r1 ? 0.0f : r2 ? 0.0f : r3 ? 0.0f : r4 ? 1.0f : r5 ? q : r6 ? q : w7;
-  const float rx = p.x - ((r.w0 * t.a.x + r.w1 * t.b.x) + r.w2 * t.c.x);
-  const float ry = p.y - ((r.w0 * t.a.y + r.w1 * t.b.y) + r.w2 * t.c.y);
-  const float rz = p.z - ((r.w0 * t.a.z + r.w1 * t.b.z) + r.w2 * t.c.z);
-  r.d = (rx * rx + ry * ry) + rz * rz;
+  const V3 res = v3_sub(p, v3_weighted(r.w0, t.a, r.w1, t.b, r.w2, t.c));
+  r.d = v3_dot_rounded(res, res);
   return r;
 }
 
@@ -97,13 +90,12 @@ __global__ __launch_bounds__(kPdThreads) void pd_records_kernel(const float* __r
   const long long x = (long long)blockIdx.x * kPdThreads + threadIdx.x;
   if (x >= rows) return;
   const long long b = x / F;
-  const long long* __restrict__ row = faces + (shared ? x - b * F : x) * 3;
-  const long long i0 = row[0], i1 = row[1], i2 = row[2];
+  const MeshFace t = mesh_face(faces, b, x - b * F, F, N, shared);
   float4 w0 = {0.0f, 0.0f, 0.0f, 0.0f}, w1 = w0, w2 = w0, w3 = w0;
-  if (!(i0 < 0 || i0 >= N || i1 < 0 || i1 >= N || i2 < 0 || i2 >= N)) {
+  if (t.in_range) {
     const float* __restrict__ vb = vertices + (size_t)b * N * 3;
-    const V3 a = md_load(vb, i0), c1 = md_load(vb, i1), c2 = md_load(vb, i2);
-    const V3 ab = md_sub(c1, a), ac = md_sub(c2, a);
+    const V3 a = v3_load(vb, t.i0), c1 = v3_load(vb, t.i1), c2 = v3_load(vb, t.i2);
+    const V3 ab = v3_sub(c1, a), ac = v3_sub(c2, a);
     w0 = {a.x, a.y, a.z, c1.x};
     w1 = {c1.y, c1.z, c2.x, c2.y};
     w2 = {c2.z, ab.x, ab.y, ab.z};
@@ -122,9 +114,7 @@ __device__ __forceinline__ void pd_store(float* __restrict__ dist, long long* __
                                          float w2) {
   dist[x] = arg < 0 ? pp::quiet_nan() : best;
   index[x] = arg;
-  bary[x * 3] = w0;
-  bary[x * 3 + 1] = w1;
-  bary[x * 3 + 2] = w2;
+  v3_store(bary, x, {w0, w1, w2});
 }
 
 __global__ __launch_bounds__(kPdThreads) void pd_point_face_kernel(const float* __restrict__ points,
@@ -139,7 +129,7 @@ __global__ __launch_bounds__(kPdThreads) void pd_point_face_kernel(const float* 
   const long long i = (long long)(blockIdx.x - (unsigned)b * blocks_per_element) * kPdThreads + t;
   const bool live = i < P;
   V3 p = {0.0f, 0.0f, 0.0f};
-  if (live) p = md_load(points + (size_t)b * P * 3, i);
+  if (live) p = v3_load(points + (size_t)b * P * 3, i);
   const float4* __restrict__ rb = records + (size_t)b * F * (kPdRecord / 4);
   float best = __builtin_inff();
   int arg = -1;
@@ -220,7 +210,7 @@ __global__ __launch_bounds__(kPdThreads) void pd_backward_kernel(
   const long long i = item_point ? item_point[x] : x - b * S;
   bool ok = f >= 0 && f < F && i >= 0 && i < P;
   long long i0 = 0, i1 = 0, i2 = 0;
-  if (ok) {
+  if (ok) {   // (the face row and the stores are written out: pp::mesh_face and v3_store change this kernel's code)
     const long long* __restrict__ row = faces + ((shared ? 0 : b * F) + f) * 3;
     i0 = row[0], i1 = row[1], i2 = row[2];
     ok = !(i0 < 0 || i0 >= N || i1 < 0 || i1 >= N || i2 < 0 || i2 >= N);
@@ -228,8 +218,8 @@ __global__ __launch_bounds__(kPdThreads) void pd_backward_kernel(
   V3 out = {0.0f, 0.0f, 0.0f}, opp = out;
   if (ok) {
     const float* __restrict__ vb = vertices + (size_t)b * N * 3;
-    const V3 a = md_load(vb, i0), c1 = md_load(vb, i1), c2 = md_load(vb, i2);
-    const V3 p = md_load(points + (size_t)b * P * 3, i);
+    const V3 a = v3_load(vb, i0), c1 = v3_load(vb, i1), c2 = v3_load(vb, i2);
+    const V3 p = v3_load(points + (size_t)b * P * 3, i);
     const float w0 = bary[x * 3], w1 = bary[x * 3 + 1], w2 = bary[x * 3 + 2];
     const float rx = p.x - ((w0 * a.x + w1 * c1.x) + w2 * c2.x);
     const float ry = p.y - ((w0 * a.y + w1 * c1.y) + w2 * c2.y);
@@ -251,20 +241,6 @@ __global__ __launch_bounds__(kPdThreads) void pd_backward_kernel(
   if (face_out) face_out[x] = ok ? f : -1;
 }
 
-// FILL = false: the points' face counts; FILL = true: the lists.  A face whose point is out of range takes no part.
-template <bool FILL>
-__global__ __launch_bounds__(kPdThreads) void pd_lists_kernel(const long long* __restrict__ point,
-                                                              unsigned* __restrict__ cursor,
-                                                              unsigned* __restrict__ entries, long long total, int F,
-                                                              int P) {
-  const long long x = (long long)blockIdx.x * kPdThreads + threadIdx.x;
-  if (x >= total) return;
-  const long long i = point[x];
-  if (i < 0 || i >= P) return;
-  const long long b = x / F;
-  pp::bucket_put<FILL>(cursor, entries, b, P, (long long)F, (size_t)i, (unsigned)(x - b * F));
-}
-
 // one lane per (b, point): the sum of vec over the point's sorted face list, plain fp32 additions from +0
 __global__ __launch_bounds__(kPdThreads) void pd_point_sums_kernel(const unsigned* __restrict__ start,
                                                                    const unsigned* __restrict__ cursor,
@@ -281,26 +257,18 @@ __global__ __launch_bounds__(kPdThreads) void pd_point_sums_kernel(const unsigne
   V3 acc = {0.0f, 0.0f, 0.0f};
   for (unsigned q = 0; q < n; ++q) {
     const unsigned e = list[q];
-    V3 term = {pp::quiet_nan(), pp::quiet_nan(), pp::quiet_nan()};
-    if (e < (unsigned)F) term = md_load(vb, e);
-    acc = {acc.x + term.x, acc.y + term.y, acc.z + term.z};
+    V3 term = v3_nan();
+    if (e < (unsigned)F) term = v3_load(vb, e);
+    acc = v3_add(acc, term);
   }
-  grad_points[i * 3] = acc.x;
-  grad_points[i * 3 + 1] = acc.y;
-  grad_points[i * 3 + 2] = acc.z;
-}
-
-// the sizes every entry checks: the rows of a launch and the slot codes fit 31 bits
-bool pd_sizes_ok(int B, int N, int F, int P) {
-  return B >= 0 && N >= 0 && F >= 0 && P >= 0 && (long long)B * N <= 0x7fffffffLL && (long long)B * F <= 0x7fffffffLL &&
-         (long long)B * P <= 0x7fffffffLL && 3LL * F <= 0x7fffffffLL;
+  v3_store(grad_points, i, acc);
 }
 
 }  // namespace
 
 extern "C" int pp_mesh_distance_records_f32(const float* vertices, const long long* faces, float* records, int B, int N,
                                             int F, int shared_topology, void* stream) {
-  if (!pd_sizes_ok(B, N, F, 0)) return PP_EINVAL;
+  if (!pp::mesh_sizes_ok(B, N, F, 0)) return PP_EINVAL;
   if (B == 0 || N == 0 || F == 0) return PP_OK;
   if (!vertices || !faces || !records || ((uintptr_t)records & 15u)) return PP_EINVAL;
   const long long rows = (long long)B * F;
@@ -312,7 +280,7 @@ extern "C" int pp_mesh_distance_records_f32(const float* vertices, const long lo
 
 extern "C" int pp_mesh_point_face_forward_f32(const float* points, const float* records, float* dist, long long* face,
                                               float* bary, int B, int P, int F, void* stream) {
-  if (!pd_sizes_ok(B, 0, F, P)) return PP_EINVAL;
+  if (!pp::mesh_sizes_ok(B, 0, F, P)) return PP_EINVAL;
   if (B == 0 || P == 0 || F == 0) return PP_OK;
   if (!points || !records || !dist || !face || !bary || ((uintptr_t)records & 15u)) return PP_EINVAL;
   const int per_element = (int)pp::blocks(P, kPdThreads);
@@ -325,7 +293,7 @@ extern "C" int pp_mesh_point_face_forward_f32(const float* points, const float* 
 
 extern "C" int pp_mesh_face_point_forward_f32(const float* points, const float* records, float* dist, long long* point,
                                               float* bary, int B, int P, int F, void* stream) {
-  if (!pd_sizes_ok(B, 0, F, P)) return PP_EINVAL;
+  if (!pp::mesh_sizes_ok(B, 0, F, P)) return PP_EINVAL;
   if (B == 0 || P == 0 || F == 0) return PP_OK;
   if (!points || !records || !dist || !point || !bary || ((uintptr_t)records & 15u)) return PP_EINVAL;
   const int per_element = (int)pp::blocks(F, kPdThreads);
@@ -342,7 +310,7 @@ extern "C" int pp_mesh_distance_backward_f32(const float* points, const float* v
                                              long long* face_out, float* grad_points, int B, int N, int F, int P,
                                              int shared_topology, void* workspace, size_t workspace_bytes,
                                              void* stream) {
-  if (!pd_sizes_ok(B, N, F, P)) return PP_EINVAL;
+  if (!pp::mesh_sizes_ok(B, N, F, P)) return PP_EINVAL;
   if (B == 0 || N == 0 || F == 0 || P == 0) return PP_OK;
   if (!points || !vertices || !faces || !bary || !grad_dist || (item_face != nullptr) == (item_point != nullptr))
     return PP_EINVAL;
@@ -359,19 +327,12 @@ extern "C" int pp_mesh_distance_backward_f32(const float* points, const float* v
   const pp::BucketLayout L = pp::bucket_layout(B, P, F, false);
   unsigned char* ws = (unsigned char*)workspace;
   if (!ws || workspace_bytes < L.total) return PP_EINVAL;
-  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
-  unsigned* entries = reinterpret_cast<unsigned*>(ws + L.entries);
-  const int rc = pp::bucket_build(ws, L, entries, nullptr, B, P, F, true, s, [&](bool fill) {
-    const dim3 grid(pp::blocks(total, kPdThreads)), block(kPdThreads);
-    if (fill)
-      pd_lists_kernel<true><<<grid, block, 0, s>>>(item_point, cursor, entries, total, F, P);
-    else
-      pd_lists_kernel<false><<<grid, block, 0, s>>>(item_point, cursor, entries, total, F, P);
-  });
+  const int rc = pp::mesh_item_lists(item_point, B, P, F, L, ws, s);   // (a face whose point is out of range: no part)
   if (rc != PP_OK) return rc;
   const long long rows = (long long)B * P;
   pd_point_sums_kernel<<<dim3(pp::blocks(rows, kPdThreads)), dim3(kPdThreads), 0, s>>>(
-      reinterpret_cast<const unsigned*>(ws + L.start), cursor, entries, vec, grad_points, rows, F, P);
+      reinterpret_cast<const unsigned*>(ws + L.start), reinterpret_cast<const unsigned*>(ws + L.cursor),
+      reinterpret_cast<const unsigned*>(ws + L.entries), vec, grad_points, rows, F, P);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }

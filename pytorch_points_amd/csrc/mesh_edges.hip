@@ -33,9 +33,11 @@
 //   apply              one thread per (b, vertex): a gather over the vertex's slice from +0 in slot order, plain fp32
 //                      operations; the uniform operator's forward and backward and the cotangent operator (whose
 //                      backward is the same call on the gradient) are three modes of one kernel
-#include "mesh_common.h"
+#include "mesh_common.h"   // pp::mesh_half_edge, mesh_build_ok, mesh_face, mesh_row, V3 and v3_*; bucket_lists.h
 
 namespace {
+
+using namespace pp;   // mesh_common.h's rows and three-vectors
 
 constexpr int kMeThreads = 256;
 constexpr int kMeScanThreads = pp::kBucketScanThreads;   // me_compact_kernel ranks with the chain's block scan
@@ -155,44 +157,27 @@ __global__ __launch_bounds__(kMeThreads) void me_sqrlen_backward_kernel(
     int N, int Ecap, int shared) {
   const long long i = (long long)blockIdx.x * kMeThreads + threadIdx.x;
   if (i >= rows) return;
-  const long long b = i / N;
-  const long long v = i - b * N;
-  const long long tb = shared ? 0 : b;
-  const float* __restrict__ vb = vertices + (size_t)b * N * 3;
-  const long long* __restrict__ eb = edges + (size_t)tb * Ecap * 2;
-  const unsigned* __restrict__ list = inc_entries + (size_t)tb * Ecap * 2;
-  const float* __restrict__ gb = g + (size_t)b * Ecap;
-  const int* __restrict__ st = inc_start + (size_t)tb * ((size_t)N + 1) + v;
-  const float px = vb[v * 3], py = vb[v * 3 + 1], pz = vb[v * 3 + 2];
-  float ax = 0.0f, ay = 0.0f, az = 0.0f;
+  const MeshRow w = mesh_row(i, N, shared);
+  const float* __restrict__ vb = vertices + (size_t)w.b * N * 3;
+  const long long* __restrict__ eb = edges + (size_t)w.tb * Ecap * 2;
+  const unsigned* __restrict__ list = inc_entries + (size_t)w.tb * Ecap * 2;
+  const float* __restrict__ gb = g + (size_t)w.b * Ecap;
+  const int* __restrict__ st = inc_start + (size_t)w.tb * ((size_t)N + 1) + w.i;   // (read as it is, not clipped)
+  const V3 p = v3_load(vb, w.i);
+  V3 acc = {0.0f, 0.0f, 0.0f};
   for (int q = st[0], q1 = st[1]; q < q1; ++q) {
     const unsigned code = list[q];
     const unsigned e = code >> 1, side = code & 1u;
     const long long o = eb[2 * (size_t)e + (side ^ 1u)];   // the other end; this end is v
     const float coef = 2.0f * gb[e];
-    float tx, ty, tz;
-    if (o < 0 || o >= N) {
-      tx = ty = tz = pp::quiet_nan();
-    } else {
-      const float ox = vb[o * 3], oy = vb[o * 3 + 1], oz = vb[o * 3 + 2];
-      // v_a - v_b with a = edges[e,0], b = edges[e,1]
-      tx = coef * (side ? ox - px : px - ox);
-      ty = coef * (side ? oy - py : py - oy);
-      tz = coef * (side ? oz - pz : pz - oz);
+    V3 t = v3_nan();
+    if (!(o < 0 || o >= N)) {
+      const V3 po = v3_load(vb, o);
+      t = v3_scale(coef, side ? v3_sub(po, p) : v3_sub(p, po));   // v_a - v_b, a = edges[e,0], b = edges[e,1]
     }
-    if (side) {
-      ax = ax - tx;
-      ay = ay - ty;
-      az = az - tz;
-    } else {
-      ax = ax + tx;
-      ay = ay + ty;
-      az = az + tz;
-    }
+    acc = side ? v3_sub(acc, t) : v3_add(acc, t);
   }
-  grad[i * 3] = ax;
-  grad[i * 3 + 1] = ay;
-  grad[i * 3 + 2] = az;
+  v3_store(grad, i, acc);
 }
 
 // ---- corners ------------------------------------------------------------------------------------------------------
@@ -228,34 +213,26 @@ __global__ __launch_bounds__(kMeThreads) void me_cotangent_kernel(const float* _
   const long long x = (long long)blockIdx.x * kMeThreads + threadIdx.x;
   if (x >= total) return;
   const long long b = x / F;
-  const long long* __restrict__ row = faces + (shared ? x - b * F : x) * 3;
-  const long long i1 = row[0], i2 = row[1], i3 = row[2];
-  float* __restrict__ o = out + x * 3;
-  if (i1 < 0 || i1 >= N || i2 < 0 || i2 >= N || i3 < 0 || i3 >= N) {
-    o[0] = o[1] = o[2] = pp::quiet_nan();
+  const MeshFace t = mesh_face(faces, b, x - b * F, F, N, shared);
+  if (!t.in_range) {
+    v3_store(out, x, v3_nan());
     return;
   }
   const float* __restrict__ vb = vertices + (size_t)b * N * 3;
-  const float* __restrict__ p1 = vb + i1 * 3;
-  const float* __restrict__ p2 = vb + i2 * 3;
-  const float* __restrict__ p3 = vb + i3 * 3;
-  auto len = [](const float* __restrict__ p, const float* __restrict__ q) {
-    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-    return sqrtf((dx * dx + dy * dy) + dz * dz);   // correctly rounded in this build
-  };
-  const float l1 = len(p2, p3), l2 = len(p3, p1), l3 = len(p1, p2);
+  const V3 p1 = v3_load(vb, t.i0), p2 = v3_load(vb, t.i1), p3 = v3_load(vb, t.i2);
+  // v3_len: sqrtf((dx*dx + dy*dy) + dz*dz), correctly rounded in this build
+  const float l1 = v3_len(v3_sub(p2, p3)), l2 = v3_len(v3_sub(p3, p1)), l3 = v3_len(v3_sub(p1, p2));
   const float sp = ((l1 + l2) + l3) * 0.5f;
   float inside = ((sp * (sp - l1)) * (sp - l2)) * (sp - l3);
   if (inside < 0.0f) inside = 0.0f;
   const float A = 2.0f * sqrtf(inside);
   if (A == 0.0f) {
-    o[0] = o[1] = o[2] = 0.0f;
+    v3_store(out, x, v3_zero());
     return;
   }
   const float s1 = l1 * l1, s2 = l2 * l2, s3 = l3 * l3, den = A + 1e-10f;
-  o[0] = (((s2 + s3) - s1) / den) / 4.0f;
-  o[1] = (((s1 + s3) - s2) / den) / 4.0f;
-  o[2] = (((s1 + s2) - s3) / den) / 4.0f;
+  const V3 w = {(((s2 + s3) - s1) / den) / 4.0f, (((s1 + s3) - s2) / den) / 4.0f, (((s1 + s2) - s3) / den) / 4.0f};
+  v3_store(out, x, w);
 }
 
 // ---- the Laplacian apply ------------------------------------------------------------------------------------------
@@ -276,15 +253,14 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
     int N, int F, long long X, int shared) {
   const long long r = (long long)blockIdx.x * kMeThreads + threadIdx.x;
   if (r >= rows) return;
-  const long long b = r / N;
-  const long long i = r - b * N;
-  const long long tb = shared ? 0 : b;
-  const float* __restrict__ xb = x + (size_t)b * N * 3;
-  const int* __restrict__ st = start + (size_t)tb * ((size_t)N + 1);
-  const int2* __restrict__ nb = reinterpret_cast<const int2*>(nbr) + (size_t)tb * (size_t)X;
-  const unsigned* __restrict__ cd = codes + (size_t)tb * (size_t)X;
-  const float* __restrict__ wb = weights + (size_t)b * F * 3;
-  const int q0 = st[i], q1 = st[i + 1];
+  const MeshRow row = mesh_row(r, N, shared);
+  const long long i = row.i;
+  const float* __restrict__ xb = x + (size_t)row.b * N * 3;
+  const int* __restrict__ st = start + (size_t)row.tb * ((size_t)N + 1);
+  const int2* __restrict__ nb = reinterpret_cast<const int2*>(nbr) + (size_t)row.tb * (size_t)X;
+  const unsigned* __restrict__ cd = codes + (size_t)row.tb * (size_t)X;
+  const float* __restrict__ wb = weights + (size_t)row.b * F * 3;
+  const int q0 = st[i], q1 = st[i + 1];   // (read as they are, not clipped)
   float px = xb[i * 3], py = xb[i * 3 + 1], pz = xb[i * 3 + 2];
   if (MODE == 1) {
     const float d = (float)(2 * (q1 - q0)) + 1e-12f;
@@ -303,7 +279,7 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
         w[0] = wb[(size_t)f * 3 + (c == 0 ? 2 : c - 1)];   // (c + 2) % 3
         w[1] = wb[(size_t)f * 3 + (c == 2 ? 0 : c + 1)];   // (c + 1) % 3
       } else {
-        w[0] = w[1] = pp::quiet_nan();
+        w[0] = w[1] = quiet_nan();
       }
     }
 #pragma unroll
@@ -311,7 +287,7 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
       const int j = side ? jk.y : jk.x;
       float ox, oy, oz;
       if (j < 0 || j >= N) {
-        ox = oy = oz = pp::quiet_nan();
+        ox = oy = oz = quiet_nan();
       } else {
         ox = xb[(size_t)j * 3];
         oy = xb[(size_t)j * 3 + 1];
@@ -340,9 +316,7 @@ __global__ __launch_bounds__(kMeThreads) void me_laplacian_apply_kernel(
     ay = ay / d;
     az = az / d;
   }
-  out[r * 3] = ax;
-  out[r * 3 + 1] = ay;
-  out[r * 3 + 2] = az;
+  v3_store(out, r, {ax, ay, az});
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------

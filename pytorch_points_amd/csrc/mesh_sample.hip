@@ -9,7 +9,7 @@
 //              CDF in LDS (every ceil(F/4096)-th entry, at most 32 KB), the last ones over global memory; then
 //              su = sqrtf(u2), w = (1 - su, su (1 - u3), su u3).  Otherwise face and w are the caller's.
 //              points_d = (w0 p0_d + w1 p1_d) + w2 p2_d, every operation rounded on its own; normals = the face's.
-//   backward   the face -> sample lists of this call (pp::bucket_build: buckets the B*F faces, items the samples,
+//   backward   the face -> sample lists of this call (pp::mesh_item_lists: buckets the B*F faces, items the samples,
 //              sorted), then
 //              stage 1, per face: gC[f][c] = sum over its samples in ascending order of w_c g_points, and
 //                       gN[f] = sum of g_normals, plain fp32 additions from +0 by one lane; a list beyond kBucketLong
@@ -23,12 +23,11 @@
 // An index of `faces` outside [0, N), a caller's `face` outside [0, F) and a slot code that names no face are only
 // compared, never used as an address: the sample's point is NaN, and in the backward the sample (or the whole face
 // with such a vertex) adds nothing.
-#include "mesh_common.h"   // pp::V3, md_load; pp::blocks, pp::quiet_nan; bucket_lists.h
+#include "mesh_common.h"   // pp::mesh_face, mesh_row, mesh_slice, mesh_item_lists, mesh_sizes_ok, V3 and v3_*
 
 namespace {
 
-using pp::V3;
-using pp::md_load;
+using namespace pp;   // mesh_common.h's rows, three-vectors and item lists; bucket_lists.h
 
 constexpr int kMsThreads = 256;
 constexpr int kMsForwardThreads = 1024;   // samples of a workgroup: they share one staged CDF
@@ -66,12 +65,6 @@ __global__ __launch_bounds__(pp::kBucketScanThreads) void ms_cdf_kernel(const fl
 }
 
 // ---- forward --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ms_store_nan(float* __restrict__ p) {
-  p[0] = pp::quiet_nan();
-  p[1] = pp::quiet_nan();
-  p[2] = pp::quiet_nan();
-}
-
 // CHOOSE: face and weights from cdf and u (u_stride floats per sample: u1, and with points u2, u3); else from face_in
 // and bary_in.  points, normals (with face_normals), face_out and bary_out may be NULL.
 template <bool CHOOSE>
@@ -98,11 +91,11 @@ __global__ __launch_bounds__(kMsForwardThreads) void ms_forward_kernel(
   if (s >= S) return;
   const size_t x = (size_t)b * S + s;
   long long f;
-  float w0, w1, w2;
+  V3 w;
   if (CHOOSE) {
     const double total = s_cdf[staged - 1];                // cdf[b, F-1]
     f = -1;
-    w0 = w1 = w2 = pp::quiet_nan();
+    w = v3_nan();
     if (total > 0.0 && total < __builtin_inf()) {
       const float* __restrict__ us = u + x * u_stride;
       const double target = (double)us[0] * total;
@@ -122,73 +115,30 @@ __global__ __launch_bounds__(kMsForwardThreads) void ms_forward_kernel(
         f = a;
         if (u_stride >= 3) {
           const float su = sqrtf(us[1]);
-          w0 = 1.0f - su;
-          w1 = su * (1.0f - us[2]);
-          w2 = su * us[2];
+          w = {1.0f - su, su * (1.0f - us[2]), su * us[2]};
         }
       }
     }
     if (face_out) face_out[x] = f;
-    if (bary_out) {
-      bary_out[x * 3] = w0;
-      bary_out[x * 3 + 1] = w1;
-      bary_out[x * 3 + 2] = w2;
-    }
+    if (bary_out) v3_store(bary_out, x, w);
   } else {
     f = face_in[x];
-    w0 = bary_in[x * 3];
-    w1 = bary_in[x * 3 + 1];
-    w2 = bary_in[x * 3 + 2];
+    w = v3_load(bary_in, x);
   }
   if (!points) return;
-  bool ok = f >= 0 && f < F;
-  long long i0 = 0, i1 = 0, i2 = 0;
-  if (ok) {
-    const long long* __restrict__ row = faces + ((shared ? 0 : b * F) + f) * 3;
-    i0 = row[0], i1 = row[1], i2 = row[2];
-    ok = !(i0 < 0 || i0 >= N || i1 < 0 || i1 >= N || i2 < 0 || i2 >= N);
-  }
-  if (!ok) {
-    ms_store_nan(points + x * 3);
-    if (normals) ms_store_nan(normals + x * 3);
+  MeshFace tri = {0, 0, 0, false};
+  if (f >= 0 && f < F) tri = mesh_face(faces, b, f, F, N, shared);
+  if (!tri.in_range) {
+    v3_store(points, x, v3_nan());
+    if (normals) v3_store(normals, x, v3_nan());
     return;
   }
   const float* __restrict__ vb = vertices + (size_t)b * N * 3;
-  const V3 p0 = md_load(vb, i0), p1 = md_load(vb, i1), p2 = md_load(vb, i2);
-  points[x * 3] = (w0 * p0.x + w1 * p1.x) + w2 * p2.x;
-  points[x * 3 + 1] = (w0 * p0.y + w1 * p1.y) + w2 * p2.y;
-  points[x * 3 + 2] = (w0 * p0.z + w1 * p1.z) + w2 * p2.z;
-  if (normals) {
-    const V3 n = md_load(face_normals, b * F + f);
-    normals[x * 3] = n.x;
-    normals[x * 3 + 1] = n.y;
-    normals[x * 3 + 2] = n.z;
-  }
+  v3_store(points, x, v3_weighted(w.x, v3_load(vb, tri.i0), w.y, v3_load(vb, tri.i1), w.z, v3_load(vb, tri.i2)));
+  if (normals) v3_store(normals, x, v3_load(face_normals, b * F + f));
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------
-// FILL = false: the faces' sample counts; FILL = true: the lists.  A sample whose face is out of range takes no part.
-template <bool FILL>
-__global__ __launch_bounds__(kMsThreads) void ms_lists_kernel(const long long* __restrict__ face,
-                                                              unsigned* __restrict__ cursor,
-                                                              unsigned* __restrict__ entries, long long total, int F,
-                                                              int S) {
-  const long long x = (long long)blockIdx.x * kMsThreads + threadIdx.x;
-  if (x >= total) return;
-  const long long f = face[x];
-  if (f < 0 || f >= F) return;
-  const long long b = x / S;
-  pp::bucket_put<FILL>(cursor, entries, b, F, (long long)S, (size_t)f, (unsigned)(x - b * S));
-}
-
-// whether face f of batch element b names three vertices in range
-__device__ __forceinline__ bool ms_face_in_range(const long long* __restrict__ faces, long long b, long long f, int N,
-                                                 int F, int shared) {
-  const long long* __restrict__ row = faces + ((shared ? 0 : b * F) + f) * 3;
-  const long long i0 = row[0], i1 = row[1], i2 = row[2];
-  return !(i0 < 0 || i0 >= N || i1 < 0 || i1 >= N || i2 < 0 || i2 >= N);
-}
-
 // the sums of one face over the entries q = first, first + step, ... < n of its list
 struct MsSums {
   float c[9], n[3];
@@ -230,11 +180,7 @@ __device__ __forceinline__ void ms_store_sums(const MsSums& a, float* __restrict
 #pragma unroll
     for (int k = 0; k < 9; ++k) gC[i * 9 + k] = a.c[k];
   }
-  if (NORMALS) {
-    gN[i * 3] = a.n[0];
-    gN[i * 3 + 1] = a.n[1];
-    gN[i * 3 + 2] = a.n[2];
-  }
+  if (NORMALS) v3_store(gN, i, {a.n[0], a.n[1], a.n[2]});
 }
 
 // stage 1: one lane per (b, face); a list beyond kBucketLong is left to ms_face_sums_long_kernel
@@ -249,7 +195,7 @@ __global__ __launch_bounds__(kMsThreads) void ms_face_sums_kernel(
   const long long b = i / F;
   const unsigned s0 = start[i];
   unsigned n = cursor[i] - s0;
-  if (!ms_face_in_range(faces, b, i - b * F, N, F, shared))
+  if (!mesh_face(faces, b, i - b * F, F, N, shared).in_range)
     n = 0;   // adds nothing
   else if (n > (unsigned)pp::kBucketLong)
     return;
@@ -271,7 +217,7 @@ __global__ __launch_bounds__(kMsLongThreads) void ms_face_sums_long_kernel(
   for (unsigned q = blockIdx.x; q < count; q += gridDim.x) {
     const unsigned i = longlist[q];
     const long long b = i / (unsigned)F;
-    if (!ms_face_in_range(faces, b, (long long)i - b * F, N, F, shared)) continue;   // (the whole workgroup)
+    if (!mesh_face(faces, b, (long long)i - b * F, F, N, shared).in_range) continue;   // (the whole workgroup)
     const unsigned s0 = start[i], n = cursor[i] - s0;
     const MsSums a = ms_list_sums<POINTS, NORMALS>(entries + (size_t)b * S + s0, (unsigned)t, (unsigned)kMsLongThreads,
                                                    n, bary, gp, gn, (size_t)b * S);
@@ -312,33 +258,19 @@ __global__ __launch_bounds__(kMsThreads) void ms_vertex_gather_kernel(const int*
                                                                       int F, int shared) {
   const long long r = (long long)blockIdx.x * kMsThreads + threadIdx.x;
   if (r >= rows) return;
-  const long long b = r / N;
-  const long long i = r - b * N;
   const long long X = 3LL * F;
-  const long long tb = shared ? 0 : b;
-  const int* __restrict__ st = start + (size_t)tb * ((size_t)N + 1) + i;
-  const unsigned* __restrict__ cd = codes + (size_t)tb * (size_t)X;
-  const float* __restrict__ gb = gC + (size_t)b * (size_t)X * 3;
-  const int lo = st[0], hi = st[1];
-  const int q0 = lo < 0 ? 0 : lo;
-  const int q1 = (long long)hi > X ? (int)X : hi;
+  const MeshRow w = mesh_row(r, N, shared);
+  const MeshSlice s = mesh_slice(start, nullptr, codes, w, N, X);
+  const float* __restrict__ gb = gC + (size_t)w.b * (size_t)X * 3;
   V3 acc = {0.0f, 0.0f, 0.0f};
-  for (int q = q0; q < q1; ++q) {
-    const unsigned code = cd[q];
-    V3 term = {pp::quiet_nan(), pp::quiet_nan(), pp::quiet_nan()};
-    if (code < (unsigned)X) term = md_load(gb, code);
-    acc = {acc.x + term.x, acc.y + term.y, acc.z + term.z};
+  for (int q = s.q0; q < s.q1; ++q) {
+    const unsigned code = s.codes[q];
+    V3 term = v3_nan();
+    if (code < (unsigned)X) term = v3_load(gb, code);
+    acc = v3_add(acc, term);
   }
-  if (extra) acc = {acc.x + extra[r * 3], acc.y + extra[r * 3 + 1], acc.z + extra[r * 3 + 2]};
-  grad[r * 3] = acc.x;
-  grad[r * 3 + 1] = acc.y;
-  grad[r * 3 + 2] = acc.z;
-}
-
-// the sizes every entry checks: the samples, the faces and the rows of a launch, and the slot codes, fit 31 bits
-bool ms_sizes_ok(int B, int N, int F, int S) {
-  return B >= 0 && N >= 0 && F >= 0 && S >= 0 && (long long)B * N <= 0x7fffffffLL && (long long)B * F <= 0x7fffffffLL &&
-         (long long)B * S <= 0x7fffffffLL && 3LL * F <= 0x7fffffffLL;
+  if (extra) acc = v3_add(acc, v3_load(extra, r));
+  v3_store(grad, r, acc);
 }
 
 template <bool POINTS, bool NORMALS>
@@ -375,7 +307,7 @@ extern "C" int pp_mesh_sample_forward_f32(const float* vertices, const long long
                                           const float* bary_in, const float* face_normals, long long* face_out,
                                           float* bary_out, float* points, float* normals, int B, int N, int F, int S,
                                           int shared_topology, void* stream) {
-  if (!ms_sizes_ok(B, N, F, S)) return PP_EINVAL;
+  if (!pp::mesh_sizes_ok(B, N, F, S)) return PP_EINVAL;
   if (B == 0 || F == 0 || S == 0 || (points && N == 0)) return PP_OK;
   const bool choose = cdf != nullptr;
   if (choose ? (!u || (u_stride != 1 && u_stride != 3) || face_in || bary_in) : (!face_in || !bary_in || !points))
@@ -405,7 +337,7 @@ extern "C" int pp_mesh_sample_backward_f32(const float* vertices, const long lon
                                            float* scratch, float* grad_vertices, int B, int N, int F, int S,
                                            int shared_topology, void* workspace, size_t workspace_bytes,
                                            void* stream) {
-  if (!ms_sizes_ok(B, N, F, S)) return PP_EINVAL;
+  if (!pp::mesh_sizes_ok(B, N, F, S)) return PP_EINVAL;
   if (B == 0 || N == 0 || F == 0 || S == 0) return PP_OK;
   if (!vertices || !faces || !start || !nbr || !codes || !face || !bary || !scratch || !grad_vertices ||
       (!grad_points && !grad_normals) || scratch == grad_vertices)
@@ -415,16 +347,7 @@ extern "C" int pp_mesh_sample_backward_f32(const float* vertices, const long lon
   if (!ws || workspace_bytes < L.total) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int sh = shared_topology != 0;
-  unsigned* cursor = reinterpret_cast<unsigned*>(ws + L.cursor);
-  unsigned* entries = reinterpret_cast<unsigned*>(ws + L.entries);
-  const long long samples = (long long)B * S;
-  int rc = pp::bucket_build(ws, L, entries, nullptr, B, F, S, true, s, [&](bool fill) {
-    const dim3 grid(pp::blocks(samples, kMsThreads)), block(kMsThreads);
-    if (fill)
-      ms_lists_kernel<true><<<grid, block, 0, s>>>(face, cursor, entries, samples, F, S);
-    else
-      ms_lists_kernel<false><<<grid, block, 0, s>>>(face, cursor, entries, samples, F, S);
-  });
+  int rc = pp::mesh_item_lists(face, B, F, S, L, ws, s);   // a sample whose face is out of range takes no part
   if (rc != PP_OK) return rc;
   // scratch: gC (B,F,3,3) | gN (B,F,3) | the normals' gradient of the vertices (B,N,3); the last two with grad_normals
   float* gC = scratch;
