@@ -722,6 +722,38 @@ int pp_mesh_distance_backward_f32(const float* points, const float* vertices, co
                                   float* grad_points, int B, int N, int F, int P, int shared_topology, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- earth mover's distance ------------------------------------------------------------------
+ * The approximate matching of Fan, Su and Guibas (2017) between fp32 clouds xyz1 (B,N,3) and xyz2 (B,M,3), every pair
+ * walked in every round; contract in DESIGN.md "Earth mover's distance".  No counterpart in the reference.
+ * d_kl = (dx*dx + dy*dy) + dz*dz; multiL = max(N,M)/N, multiR = max(N,M)/M (integer division); L = 10 levels,
+ * level_j = -4^(7-j) for j = 0..8 and level_9 = 0; exp(level*d) is exp2 of d * (level * log2 e).  From remainL = multiL,
+ * remainR = multiR, per level: a[k] = remainL[k] / (1e-9 + sum_l exp(level d) remainR[l]); s[l] = (sum_k exp(level d)
+ * a[k]) remainR[l]; b[l] = min(remainR[l] / (s[l] + 1e-9), 1) remainR[l]; remainR[l] = max(0, remainR[l] - s[l]);
+ * remainL[k] = max(0, remainL[k] - a[k] sum_l exp(level d) b[l]).  The match is never stored:
+ * match[k,l] = sum_j (exp(level_j d_kl) a_j[k]) b_j[l], j ascending, xyz1 along the rows.
+ * Every sum over N or M is four partial sums over the indices = 0, 1, 2, 3 (mod 4), each ascending from +0, added as
+ * ((p0 + p1) + p2) + p3.  No floating-point atomics: identical on every run.  No loop bound or address depends on the
+ * data; what NaN or infinite coordinates give is outside the contract.
+ * Every entry returns PP_EINVAL where a size is negative or B*N or B*M exceeds 2^31 - 1, before any launch, and PP_OK
+ * without a launch (and without a write) where B, N or M is 0.  N*M itself may exceed 2^31.
+ * pp_emd_workspace_bytes: host arithmetic; the bytes pp_emd_match_f32 and pp_emd_cost_f32 need, 0 for a refused shape.
+ * pp_emd_match_f32: the factors a (B,10,N) and b (B,10,M), twenty launches.
+ * pp_emd_dense_f32: match (B,N,M) from the factors, indexed in 64 bits.
+ * pp_emd_cost_f32: cost (B,) = sum_kl match[k,l] sqrt(d_kl); the rows' sums go through `workspace` and are added per
+ *   batch element by lane t over the rows t, t + 256, ... and a binary tree over the 256 lanes.
+ * pp_emd_cost_backward_f32: the match held constant: grad_xyz1[k] = grad_cost[b] * sum_l (match[k,l] / max(sqrt(d_kl),
+ *   1e-20)) (xyz1_k - xyz2_l), grad_xyz2[l] the same over k with (xyz2_l - xyz1_k); overwritten; either may be NULL. */
+size_t pp_emd_workspace_bytes(int B, int N, int M);
+int pp_emd_match_f32(const float* xyz1, const float* xyz2, float* a, float* b, int B, int N, int M, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int pp_emd_dense_f32(const float* xyz1, const float* xyz2, const float* a, const float* b, float* match, int B, int N,
+                     int M, void* stream);
+int pp_emd_cost_f32(const float* xyz1, const float* xyz2, const float* a, const float* b, float* cost, int B, int N,
+                    int M, void* workspace, size_t workspace_bytes, void* stream);
+int pp_emd_cost_backward_f32(const float* xyz1, const float* xyz2, const float* a, const float* b,
+                             const float* grad_cost, float* grad_xyz1, float* grad_xyz2, int B, int N, int M,
+                             void* stream);
+
 /* The library also exports pp_debug_set_* switches that force one kernel variant or another; they
  * exist for the parity tests and for tuning and are deliberately not declared here. */
 

@@ -66,6 +66,8 @@ def furthest_sampling_status(device):
     device = torch.device(device)
     status = 0
     for ws in _lib.cached_workspaces("fps", device):
+        if not getattr(ws, "_pp_status_zeroed", False):
+            continue   # a buffer no furthest_sampling call has used yet: its word is whatever the allocator left
         with _lib.on_device(device) as stream:
             status |= int(_lib.lib().pp_furthest_sampling_status(_lib.ptr(ws), stream))
     return status

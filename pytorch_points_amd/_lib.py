@@ -133,6 +133,11 @@ SIGNATURES = {
     "pp_mesh_point_face_forward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pp_mesh_face_point_forward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pp_mesh_distance_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_emd_workspace_bytes": [_I, _I, _I],
+    "pp_emd_match_f32": [_P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_emd_dense_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "pp_emd_cost_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_emd_cost_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
 }
 _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_bytes": _c_size_t,
              "pp_nmdistance_forward_workspace_bytes": _c_size_t,
@@ -143,7 +148,7 @@ _RESTYPES = {"pp_version": ctypes.c_char_p, "pp_furthest_sampling_workspace_byte
              "pp_gc3d_workspace_bytes": _c_size_t, "pp_mvc2d_workspace_bytes": _c_size_t,
              "pp_gc2d_workspace_bytes": _c_size_t,
              "pp_knn_edges_workspace_bytes": _c_size_t, "pp_edge_features_workspace_bytes": _c_size_t,
-             "pp_mesh_edges_workspace_bytes": _c_size_t}
+             "pp_mesh_edges_workspace_bytes": _c_size_t, "pp_emd_workspace_bytes": _c_size_t}
 
 _lib = None
 

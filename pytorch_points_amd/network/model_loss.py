@@ -553,3 +553,23 @@ class MeshLaplacianLoss(torch.nn.Module):
             return self.metric(lap1, lap2)
         else:
             return lap1.mean()
+
+
+class EarthMoverLoss(torch.nn.Module):
+    """``emd_distance(xyz1, xyz2) / max(N,M)``, the cost of the approximate matching per unit of mass, reduced over the
+    batch by ``"mean"``, ``"sum"`` or ``"none"`` (no counterpart in the reference)."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("EarthMoverLoss: reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+        self.reduction = reduction
+
+    def forward(self, xyz1, xyz2):
+        from .. import emd as _emd
+        per_cloud = _emd.emd_distance(xyz1, xyz2) / max(xyz1.shape[1], xyz2.shape[1], 1)
+        if self.reduction == "mean":
+            return per_cloud.mean()
+        if self.reduction == "sum":
+            return per_cloud.sum()
+        return per_cloud
