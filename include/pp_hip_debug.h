@@ -73,16 +73,38 @@ void pp_debug_set_ball_query_lpc(int lanes_per_centre);
  * (the same chunks of positions), 2 / 4 / 8 and the other values above 100 its one register-staged LDS kernel; a value
  * that names an LDS form takes it below the automatic choice's 256 * 2048 positions as well (aligned shapes only) */
 void pp_debug_set_group_points_variant(int variant);
-/* group_points_grad: 0 automatic, 1 global atomics, 2 the double LDS column also below 4096 positions; any other
- * value means 0 */
+/* group_points_grad: 0 automatic, 1 no double LDS column (fp32 without a sorted form: global atomics), 2 the double
+ * LDS column also below 4096 positions; any other value means 0.  One policy reads it for fp32 and 16-bit tensors: 2
+ * lowers the column's floor and leaves the sorted form its precedence for short lists of big problems */
 void pp_debug_set_group_points_grad_variant(int variant);
 void pp_debug_set_three_nn_search(int mode);       /* 0 automatic, 1 scan */
 /* three_interpolate: 0 automatic, 1 the global-gather kernel, 2 no channel-group form (fp32: the row-at-a-time LDS form
  * where it applies; 16-bit: the global form); 3 = the 16-bit dispatch takes its channel-group form wherever the rows
- * fit (the fp32 dispatch reads 3 as 0).  The *_grad_* knobs and the scatter mode mean the same to both dispatches */
+ * fit (the fp32 dispatch reads 3 as 0) */
 void pp_debug_set_three_interpolate_variant(int variant);
+/* three_interpolate_grad: 0 automatic, 1 and 3 no double LDS column (fp32: the sorted form for big problems with a
+ * workspace, else global atomics; 16-bit: the sorted form), 2 the double LDS column also below 2048 points */
 void pp_debug_set_three_interpolate_grad_variant(int variant);
-void pp_debug_set_scatter_mode(int mode);          /* 1 = never use the sorted scatter-add form */
+/* 1 = never use the sorted scatter-add form (the ordered form of deterministic mode is not a choice and stays) */
+void pp_debug_set_scatter_mode(int mode);
+/* The form the scatter-add backwards' one policy (sampling.hip: scatter_plan) picks for a described call under the
+ * three knobs above as they stand: pure host arithmetic, no HIP call.  op and the result are the values below;
+ * elem_bytes 4 = fp32, 2 = f16 / bf16; write: the entry WRITES its output (*_out_ws_*) rather than accumulating -- the
+ * form does not depend on it, the zero fill in front of an accumulating form does; ordered: an *_ordered_* entry or
+ * the 16-bit entries' flag; sources per batch element: M of gather_backward, npoint * nsample of group_points_grad, N
+ * of three_interpolate_grad; destinations: N, N, M; workspace_bytes: what the caller passes beside a non-null
+ * workspace (0: none).  PP_SCATTER_FORM_NONE is the entry's PP_ENOTSUP.  -1: the arguments describe no call (unknown
+ * op or element size, a size <= 0: the entries serve those before any form is chosen) */
+enum { PP_SCATTER_GATHER = 0, PP_SCATTER_GROUP = 1, PP_SCATTER_INTERPOLATE = 2 };
+enum {
+  PP_SCATTER_FORM_NONE = 0,
+  PP_SCATTER_FORM_ATOMICS = 1, /* global atomicAdd (fp32 only) */
+  PP_SCATTER_FORM_COLUMN = 2,  /* double accumulators in the LDS */
+  PP_SCATTER_FORM_SORTED = 3,  /* sorted triples in the workspace */
+  PP_SCATTER_FORM_ORDERED = 4  /* sorted triples, ascending source order per destination */
+};
+int pp_debug_scatter_plan(int op, int elem_bytes, int write, int ordered, int B, int C, long long sources,
+                          int destinations, size_t workspace_bytes);
 void pp_debug_set_knn_search(int mode);            /* 0 automatic, 1 scan */
 /* a pure streaming store of `bytes` (16-byte stores, non-temporal or plain, `workgroups` x 1024 threads): the store
  * ceiling bench.py reports beside group_points (roofline.peak_measured) */

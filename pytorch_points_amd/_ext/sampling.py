@@ -161,6 +161,24 @@ def _served16(code, what):
     return True
 
 
+def _scatter_backward(dev, dt, stem, fp32_kind, problem, args, what, what_ordered):
+    """The shared tail of the scatter-add backwards.  ``problem``: (B, triples, destinations, per_source, weighted) of
+    pp_scatter_workspace_bytes; ``args``: the entry points' arguments up to the workspace.
+    16-bit ``dt``: the ``<stem>_out_ws_<type>`` entry with the ``ordered`` flag; False = no atomic-free form serves
+    the shape, and the caller widens, runs the fp32 path and rounds.  fp32: ``<stem>_ordered_f32`` in deterministic
+    mode (ordered_or_fallback), else ``<stem>_<fp32_kind>_f32`` ("ws" accumulates, "out_ws" writes); True."""
+    with _lib.on_device(dev) as stream:
+        ws, nbytes = _scatter_ws(dev, *problem)
+        args = (*args, _lib.ptr(ws) if ws is not None else None, nbytes)
+        det = _lib.deterministic()
+        if dt is not torch.float32:
+            return _served16(_entry16("%s_out_ws" % stem, dt)(*args, 1 if det else 0, stream), what)
+        L = _lib.lib()
+        if not (det and _lib.ordered_or_fallback(getattr(L, "%s_ordered_f32" % stem)(*args, stream), what_ordered)):
+            _lib.check(getattr(L, "%s_%s_f32" % (stem, fp32_kind))(*args, stream), what)
+    return True
+
+
 def gather_forward(b, c, n, npoints, points, idx, out):
     """gather_points_wrapper_fast (sampling.cpp:19-28): out[b,c,m] = points[b,c,idx[b,m]]"""
     dev = _lib.require_cuda(("points", points), ("idx", idx), ("out", out))
@@ -185,20 +203,12 @@ def gather_backward(b, c, n, npoints, grad_out, idx, grad_points):
     if (grad_out.numel() != b * c * npoints or idx.numel() != b * npoints
             or grad_points.numel() != b * c * n):
         raise RuntimeError("gather_backward: tensor sizes do not match (b, c, n, npoints)")
-    with _lib.on_device(dev) as stream:
-        ws, nbytes = _scatter_ws(dev, b, npoints, n, 1, 0)
-        args = (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad_points), b, c, n, npoints,
-                _lib.ptr(ws) if ws is not None else None, nbytes, stream)
-        L = _lib.lib()
-        if dt is not torch.float32:
-            ordered = 1 if _lib.deterministic() else 0
-            if not _served16(_entry16("pp_gather_backward_out_ws", dt)(*args[:-1], ordered, stream), "gather_backward"):
-                wide = torch.zeros(grad_points.shape, dtype=torch.float32, device=dev)
-                gather_backward(b, c, n, npoints, grad_out.float(), idx, wide)
-                grad_points.copy_(wide)
-            return 1
-        if not (_lib.deterministic() and _lib.ordered_or_fallback(L.pp_gather_backward_ordered_f32(*args), "gather_backward")):
-            _lib.check(L.pp_gather_backward_ws_f32(*args), "gather_backward")
+    if not _scatter_backward(dev, dt, "pp_gather_backward", "ws", (b, npoints, n, 1, 0),
+                             (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad_points), b, c, n, npoints),
+                             "gather_backward", "gather_backward"):
+        wide = torch.zeros(grad_points.shape, dtype=torch.float32, device=dev)
+        gather_backward(b, c, n, npoints, grad_out.float(), idx, wide)
+        grad_points.copy_(wide)
     return 1
 
 
@@ -264,28 +274,24 @@ def group_points_grad(grad_out, idx, n):
     dev = _lib.require_cuda(("grad_out", grad_out), ("idx", idx))
     if grad_out.dim() != 4 or idx.dim() != 3:
         raise RuntimeError("grad_out must be (B, C, npoint, nsample) and idx (B, npoint, nsample)")
-    b, c, npoint, nsample = grad_out.shape
-    # (the deterministic form accumulates into zeros, as the reference's does; the default form WRITES every element:
-    #  no fill in front of it, no read of the output -- pp_group_points_grad_out_ws_f32)
-    det = _lib.deterministic()
-    if dt is not torch.float32:   # (the 16-bit entry points write every element in both modes)
-        out = torch.empty(b, c, int(n), dtype=dt, device=dev)
-        with _lib.on_device(dev) as stream:
-            ws, nbytes = _scatter_ws(dev, b, npoint * nsample, int(n), 1, 0)
-            code = _entry16("pp_group_points_grad_out_ws", dt)(
-                _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(out), b, c, int(n), npoint, nsample, c * npoint * nsample,
-                _lib.ptr(ws) if ws is not None else None, nbytes, 1 if det else 0, stream)
-        if not _served16(code, "group_points_grad"):
-            return group_points_grad(grad_out.float(), idx, n).to(dt)
-        return out
-    out = (torch.zeros if det else torch.empty)(b, c, int(n), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev) as stream:
-        ws, nbytes = _scatter_ws(dev, b, npoint * nsample, int(n), 1, 0)
-        args = (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(out), b, c, int(n), npoint, nsample,
-                c * npoint * nsample, _lib.ptr(ws) if ws is not None else None, nbytes, stream)
-        L = _lib.lib()
-        if not (det and _lib.ordered_or_fallback(L.pp_group_points_grad_ordered_f32(*args), "group_points_grad")):
-            _lib.check(L.pp_group_points_grad_out_ws_f32(*args), "group_points_grad")
+    return _group_points_grad_slice(grad_out, idx, n, 0, grad_out.size(1), dt, dev, "group_points_grad")
+
+
+def _group_points_grad_slice(grad_out, idx, n, channel_offset, channels, dt, dev, what):
+    """group_points_grad of the checked grad_out[:, channel_offset : channel_offset + channels] -> (B,channels,n)"""
+    b, ctot, npoint, nsample = grad_out.shape
+    p = npoint * nsample
+    # (the deterministic fp32 form accumulates into zeros, as the reference's does; the default form WRITES every
+    #  element: no fill in front of it, no read of the output -- pp_group_points_grad_out_ws_f32; the 16-bit entry
+    #  points write every element in both modes)
+    zeroed = dt is torch.float32 and _lib.deterministic()
+    out = (torch.zeros if zeroed else torch.empty)(b, channels, int(n), dtype=dt, device=dev)
+    first = _lib._c_void_p(grad_out.data_ptr() + grad_out.element_size() * channel_offset * p)
+    if not _scatter_backward(dev, dt, "pp_group_points_grad", "out_ws", (b, p, int(n), 1, 0),
+                             (first, _lib.ptr(idx), _lib.ptr(out), b, channels, int(n), npoint, nsample, ctot * p),
+                             what, "group_points_grad"):
+        part = grad_out[:, channel_offset:channel_offset + channels].float()   # (the slice alone is widened)
+        return group_points_grad(part, idx, n).to(dt)
     return out
 
 
@@ -322,29 +328,7 @@ def group_points_grad_from(grad_out, idx, n, channel_offset, channels):
     b, ctot, npoint, nsample = grad_out.shape
     if channel_offset < 0 or channel_offset + channels > ctot:
         raise RuntimeError("channel slice out of range")
-    p = npoint * nsample
-    det = _lib.deterministic()
-    if dt is not torch.float32:
-        out = torch.empty(b, channels, int(n), dtype=dt, device=dev)
-        with _lib.on_device(dev) as stream:
-            ws, nbytes = _scatter_ws(dev, b, p, int(n), 1, 0)
-            code = _entry16("pp_group_points_grad_out_ws", dt)(
-                _lib._c_void_p(grad_out.data_ptr() + 2 * channel_offset * p), _lib.ptr(idx), _lib.ptr(out), b, channels,
-                int(n), npoint, nsample, ctot * p, _lib.ptr(ws) if ws is not None else None, nbytes, 1 if det else 0,
-                stream)
-        if not _served16(code, "group_points_grad_from"):
-            part = grad_out[:, channel_offset:channel_offset + channels].float()   # (the slice alone is widened)
-            return group_points_grad(part, idx, n).to(dt)
-        return out
-    out = (torch.zeros if det else torch.empty)(b, channels, int(n), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev) as stream:
-        ws, nbytes = _scatter_ws(dev, b, p, int(n), 1, 0)
-        args = (_lib._c_void_p(grad_out.data_ptr() + 4 * channel_offset * p), _lib.ptr(idx), _lib.ptr(out),
-                b, channels, int(n), npoint, nsample, ctot * p, _lib.ptr(ws) if ws is not None else None, nbytes, stream)
-        L = _lib.lib()
-        if not (det and _lib.ordered_or_fallback(L.pp_group_points_grad_ordered_f32(*args), "group_points_grad")):
-            _lib.check(L.pp_group_points_grad_out_ws_f32(*args), "group_points_grad_from")
-    return out
+    return _group_points_grad_slice(grad_out, idx, n, channel_offset, channels, dt, dev, "group_points_grad_from")
 
 
 def three_nn_wrapper(b, n, m, unknown, known, dist2, idx):
@@ -395,19 +379,9 @@ def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_point
     if grad_out.numel() != b * c * n or idx.numel() != b * n * 3 or weight.numel() != b * n * 3 \
             or grad_points.numel() != b * c * m:
         raise RuntimeError("three_interpolate_grad_wrapper: tensor sizes do not match (b, c, n, m)")
-    with _lib.on_device(dev) as stream:
-        ws, nbytes = _scatter_ws(dev, b, 3 * n, m, 3, 1)
-        args = (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_points), b, c, n, m,
-                _lib.ptr(ws) if ws is not None else None, nbytes, stream)
-        L = _lib.lib()
-        if dt is not torch.float32:
-            ordered = 1 if _lib.deterministic() else 0
-            if not _served16(_entry16("pp_three_interpolate_grad_out_ws", dt)(*args[:-1], ordered, stream),
-                             "three_interpolate_grad_wrapper"):
-                wide = torch.zeros(grad_points.shape, dtype=torch.float32, device=dev)
-                three_interpolate_grad_wrapper(b, c, n, m, grad_out.float(), idx, weight, wide)
-                grad_points.copy_(wide)
-            return
-        if not (_lib.deterministic() and _lib.ordered_or_fallback(L.pp_three_interpolate_grad_ordered_f32(*args),
-                                                                  "three_interpolate_grad")):
-            _lib.check(L.pp_three_interpolate_grad_ws_f32(*args), "three_interpolate_grad_wrapper")
+    if not _scatter_backward(dev, dt, "pp_three_interpolate_grad", "ws", (b, 3 * n, m, 3, 1),
+                             (_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_points), b, c, n, m),
+                             "three_interpolate_grad_wrapper", "three_interpolate_grad"):
+        wide = torch.zeros(grad_points.shape, dtype=torch.float32, device=dev)
+        three_interpolate_grad_wrapper(b, c, n, m, grad_out.float(), idx, weight, wide)
+        grad_points.copy_(wide)

@@ -1156,21 +1156,6 @@ extern "C" int pp_gather_forward_f32(const float* points, const int* idx, float*
   return PP_OK;
 }
 
-extern "C" int pp_gather_backward_f32(const float* grad_out, const int* idx, float* grad_points,
-                                      int B, int C, int N, int M, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || M == 0) return PP_OK;
-  if (!grad_out || !idx || !grad_points || N == 0) return PP_EINVAL;
-  const long long cols = (M + 255) / 256;
-  const int cpb = pick_c_per_block(cols, B, C);
-  const long long gy = (C + cpb - 1) / cpb;
-  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  gather_bwd_kernel<<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                      (hipStream_t)stream>>>(grad_out, idx, grad_points, C, N, M, cpb);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
 // 0 = automatic; 1 = force the one-wave-per-64-centres kernel (tests and tuning)
 static pp::Knob g_ball_variant;
 extern "C" void pp_debug_set_ball_query_variant(int v) { g_ball_variant.set(v); }
@@ -1312,83 +1297,6 @@ extern "C" int pp_group_points_strided_f32(const float* points, const int* idx, 
   return PP_OK;
 }
 
-// 0 = automatic; 1 = force global atomics; 2 = the double LDS column also below 4096 positions; every other value
-// means 0 (tests and tuning)
-static pp::Knob g_group_grad_variant;
-extern "C" void pp_debug_set_group_points_grad_variant(int v) { g_group_grad_variant.set(v); }
-
-extern "C" int pp_group_points_grad_f32(const float* grad_out, const int* idx, float* grad_points,
-                                        int B, int C, int N, int npoint, int nsample,
-                                        void* stream) {
-  return pp_group_points_grad_strided_f32(grad_out, idx, grad_points, B, C, N, npoint, nsample,
-                                          (long long)C * npoint * nsample, stream);
-}
-
-static int group_points_grad_launch(const float* grad_out, const int* idx, float* grad_points, int B, int C, int N,
-                                    int npoint, int nsample, long long grad_out_batch_stride, void* stream,
-                                    bool overwrite);
-static int zero_f32(float* p, size_t n, hipStream_t s) {  // (pp::fill_bytes: not hipMemsetAsync)
-  return (int)pp::fill_bytes(p, 0, n * sizeof(float), s);
-}
-
-extern "C" int pp_group_points_grad_strided_f32(const float* grad_out, const int* idx, float* grad_points,
-                                                int B, int C, int N, int npoint, int nsample,
-                                                long long grad_out_batch_stride, void* stream) {
-  return group_points_grad_launch(grad_out, idx, grad_points, B, C, N, npoint, nsample, grad_out_batch_stride, stream,
-                                  false);
-}
-// overwrite: grad_points need not be zero on entry -- the LDS-column form writes every element once (no read of the
-// output, no fill in front of it: 2 x 256 MB less traffic at config 4); the other forms zero it themselves first
-static int group_points_grad_launch(const float* grad_out, const int* idx, float* grad_points, int B, int C, int N,
-                                    int npoint, int nsample, long long grad_out_batch_stride, void* stream,
-                                    bool overwrite) {
-  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
-  const long long P = (long long)npoint * nsample;
-  const long long gbs = grad_out_batch_stride;
-  if (gbs < (long long)C * P) return PP_EINVAL;
-  if (B == 0 || C == 0 || P == 0) return PP_OK;
-  if (!grad_out || !idx || !grad_points || N == 0) return PP_EINVAL;
-  // LDS-column forms: 16-byte aligned streams, enough work per column
-  const bool vec = (uintptr_t)grad_out % 16 == 0 && (uintptr_t)idx % 16 == 0 && P % 4 == 0 && gbs % 4 == 0;
-  if (g_group_grad_variant != 1 && 8LL * ((B + 7) / 8) * C <= 0x7fffffffLL &&
-      (g_group_grad_variant == 2 || P >= 4096)) {
-    constexpr int kW64 = 152 * 1024 / 8;  // destinations per workgroup with a double column
-    const int nsplit = (N + kW64 - 1) / kW64;
-    const long long wgs = 8LL * ((B + 7) / 8) * C * nsplit;
-    if (nsplit <= 16 && wgs <= 0x7fffffffLL) {
-      const int W = nsplit == 1 ? N : kW64;
-      static pp::DeviceFlags lds64_ok, lds64s_ok;
-      if (vec) {
-        const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, true>, 152 * 1024, lds64_ok);
-        if (e != hipSuccess) return (int)e;
-        group_points_grad_lds64_kernel<8, true><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double),
-                                                  (hipStream_t)stream>>>(grad_out, idx, grad_points, B, C, N, P,
-                                                                         gbs, nsplit, W, overwrite ? 1 : 0);
-      } else {
-        const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, false>, 152 * 1024, lds64s_ok);
-        if (e != hipSuccess) return (int)e;
-        group_points_grad_lds64_kernel<8, false><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double),
-                                                   (hipStream_t)stream>>>(grad_out, idx, grad_points, B, C, N, P,
-                                                                          gbs, nsplit, W, overwrite ? 1 : 0);
-      }
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
-    }
-  }
-  if (overwrite) {  // (global atomics accumulate)
-    const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
-    if (e != PP_OK) return e;
-  }
-  const long long cols = (P + 255) / 256;
-  const int cpb = pick_c_per_block(cols, B, C);
-  const long long gy = (C + cpb - 1) / cpb;
-  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  group_points_grad_kernel<<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                             (hipStream_t)stream>>>(grad_out, idx, grad_points, C, N, P, cpb, gbs);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
 static int three_nn_launch(const float* unknown, const float* known, float* dist2, int* idx, int B, int N,
                            int M, const pp::GridSet* skip, void* stream) {
   if (B < 0 || N < 0 || M < 0) return PP_EINVAL;
@@ -1457,43 +1365,26 @@ extern "C" int pp_three_interpolate_f32(const float* points, const int* idx, con
   return PP_OK;
 }
 
-// 0 = automatic; 1 = force global atomics; 2 = force the LDS-column form and, in the _ws entry point,
-// skip the sorted form; 3 = the _ws entry point prefers the sorted form (tests and tuning)
+// ================================================================================================
+// The scatter-add backwards: gather_backward, group_points_grad, three_interpolate_grad, for fp32 and 16-bit features
+// (DESIGN.md §4).  Every entry point describes its call as a ScatterDesc; scatter_plan -- host arithmetic on the
+// description and the three knobs, nothing else -- names the form, and scatter_run validates, serves the empty sizes,
+// zero-fills where an accumulating form stands behind an entry that promises a write, and launches.
+//   atomics  the reference's global atomicAdd kernels (fp32 only: there are no 16-bit floating-point atomics)
+//   column   double accumulators in the LDS (group_points_grad_lds64_kernel, three_interpolate_grad_lds64_kernel)
+//   sorted   the sorted triples of scatter.hip (pp::ssa_run) in the caller's workspace
+//   ordered  the same with every destination's terms added in ascending source order (deterministic mode): no
+//            atomics on floating-point data, bit-equal to a sequential loop in the reference's launch order
+// fp32 outputs are ACCUMULATED into by every form but group's column with `overwrite`; 16-bit outputs are WRITTEN.
+// ================================================================================================
+// group_points_grad: 0 = automatic; 1 = no double column; 2 = the column also below 4096 positions; every other
+// value means 0.  three_interpolate_grad: 0 = automatic; 1 and 3 = no double column; 2 = the column also below 2048
+// points.  scatter mode: 1 = never the sorted form (the ordered form is an entry's contract, not a choice).
+static pp::Knob g_group_grad_variant;
+extern "C" void pp_debug_set_group_points_grad_variant(int v) { g_group_grad_variant.set(v); }
 static pp::Knob g_interp_grad_variant;
 extern "C" void pp_debug_set_three_interpolate_grad_variant(int v) { g_interp_grad_variant.set(v); }
-
-extern "C" int pp_three_interpolate_grad_f32(const float* grad_out, const int* idx,
-                                             const float* weight, float* grad_points, int B,
-                                             int C, int N, int M, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || N == 0) return PP_OK;
-  if (!grad_out || !idx || !weight || !grad_points || M == 0) return PP_EINVAL;
-  // LDS columns in double: the column(s) fit, enough points per column to pay for zeroing/flushing it
-  const size_t col = (size_t)M * sizeof(double);
-  if (g_interp_grad_variant != 1 && g_interp_grad_variant != 3 && col <= 152 * 1024 &&
-      (g_interp_grad_variant == 2 || N >= 2048)) {
-    hipStream_t s = (hipStream_t)stream;
-    if (C >= 4 && 4 * col <= 152 * 1024)
-      return launch_three_interpolate_grad_lds64<4>(grad_out, idx, weight, grad_points, B, C, N, M, s);
-    if (C >= 2 && 2 * col <= 152 * 1024)
-      return launch_three_interpolate_grad_lds64<2>(grad_out, idx, weight, grad_points, B, C, N, M, s);
-    return launch_three_interpolate_grad_lds64<1>(grad_out, idx, weight, grad_points, B, C, N, M, s);
-  }
-  const long long cols = (N + 255) / 256;
-  const int cpb = pick_c_per_block(cols, B, C);
-  const long long gy = (C + cpb - 1) / cpb;
-  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  three_interpolate_grad_kernel<<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                                  (hipStream_t)stream>>>(grad_out, idx, weight, grad_points, C, N,
-                                                         M, cpb);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
-// ---- scatter-add backwards with a caller-provided workspace: sorted triples instead of atomics ----
-// (scatter.hip).  Each falls back to its atomic form when the workspace is absent / too small or
-// the problem does not qualify (destinations per batch element > 20480, tiny problems).
-static pp::Knob g_scatter_mode;  // 0 = automatic; 1 = never use the sorted form (tests and tuning)
+static pp::Knob g_scatter_mode;
 extern "C" void pp_debug_set_scatter_mode(int v) { g_scatter_mode.set(v); }
 
 extern "C" size_t pp_scatter_workspace_bytes(int B, long long triples_per_batch, int destinations,
@@ -1502,120 +1393,281 @@ extern "C" size_t pp_scatter_workspace_bytes(int B, long long triples_per_batch,
   return pp::ssa_workspace_bytes(B, triples_per_batch, per_source, destinations, weighted != 0);
 }
 
-static bool scatter_ok(int B, int C, long long P, int R, int Nd, int weighted, const void* ws, size_t bytes) {
-  if (g_scatter_mode == 1 || !ws || C < 1) return false;
-  if ((long long)B * P * C < (1LL << 20)) return false;  // too small to pay for the sort
-  const size_t need = pp::ssa_workspace_bytes(B, P, R, Nd, weighted != 0);
-  return need != 0 && bytes >= need;
+namespace {
+
+constexpr int kColumnLds = 152 * 1024;   // the LDS a double column may take
+constexpr int kW64 = kColumnLds / 8;     // destinations per workgroup with a double column
+
+// out[b, c, dst[b, p]] += (weight ? weight[b, p] : 1) * src[b * src_bstride + c * (P / R) + p / R], in the terms of
+// pp_scatter_workspace_bytes
+struct ScatterDesc {
+  int op, B, C;           // PP_SCATTER_GATHER / _GROUP / _INTERPOLATE
+  long long P;            // triples per batch element; < 0 when the entry was passed a negative size
+  int R, Nd;              // triples per source, destinations per batch element
+  bool weighted;
+  long long src_bstride;
+  int elem_bytes = 4;     // 4 = float, 2 = f16 / bf16 (scatter_run fills it in from its element type)
+  bool write = false, ordered = false;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  ScatterDesc with(bool write_, bool ordered_, void* ws_, size_t bytes) const {
+    ScatterDesc d = *this;
+    d.write = write_, d.ordered = ordered_, d.ws = ws_, d.ws_bytes = ws_ ? bytes : 0;
+    return d;
+  }
+};
+
+ScatterDesc gather_desc(int B, int C, int N, int M) {
+  return {PP_SCATTER_GATHER, B, C, N < 0 ? -1 : M, 1, N, false, (long long)C * M};
+}
+ScatterDesc group_desc(int B, int C, int N, int npoint, int nsample, long long grad_out_batch_stride) {
+  const bool neg = N < 0 || npoint < 0 || nsample < 0;
+  return {PP_SCATTER_GROUP, B, C, neg ? -1 : (long long)npoint * nsample, 1, N, false, grad_out_batch_stride};
+}
+ScatterDesc interp_desc(int B, int C, int N, int M) {
+  return {PP_SCATTER_INTERPOLATE, B, C, M < 0 ? -1 : 3LL * N, 3, M, true, (long long)C * N};
 }
 
+struct ScatterKnobs {
+  int group, interp, scatter;
+};
+
+// The policy, for B, C, P, Nd > 0.  Measured on the MI355X: at config 4 (16 triples per destination) the sorted form
+// moves more bytes through each CU than group's column spends on its LDS atomics (6.3 vs 5.8 ms), and wins where the
+// lists are short (P <= 4 Nd); interpolate's column (0.18 ms at B=32, C=128, N=16384, M=4096) beats the sorted form
+// (0.55 ms) wherever it fits; below 2^20 products the sort does not pay for itself against fp32 atomics.
+int scatter_plan(const ScatterDesc& d, const ScatterKnobs& k) {
+  const size_t need = pp::ssa_workspace_bytes(d.B, d.P, d.R, d.Nd, d.weighted);
+  const bool fits = need != 0 && d.ws_bytes >= need;   // (need == 0: more than 20480 destinations, too many chunks)
+  if (d.ordered) return fits ? PP_SCATTER_FORM_ORDERED : PP_SCATTER_FORM_NONE;
+  const bool sorted = fits && k.scatter != 1;
+  const bool big = (long long)d.B * d.P * d.C >= (1LL << 20);
+  const bool f32 = d.elem_bytes == 4;
+  // where no column applies: fp32 has its atomics and sorts only what is big; 16-bit sorts or has no form at all
+  const int rest = f32 ? (sorted && big ? PP_SCATTER_FORM_SORTED : PP_SCATTER_FORM_ATOMICS)
+                       : (sorted ? PP_SCATTER_FORM_SORTED : PP_SCATTER_FORM_NONE);
+  if (d.op == PP_SCATTER_GROUP) {
+    if (sorted && big && d.P <= 4LL * d.Nd) return PP_SCATTER_FORM_SORTED;
+    const int nsplit = (d.Nd + kW64 - 1) / kW64;   // the column in destination ranges, at most 16 passes over grad_out
+    if (k.group != 1 && (k.group == 2 || d.P >= 4096) && nsplit <= 16 &&
+        8LL * ((d.B + 7) / 8) * d.C * nsplit <= 0x7fffffffLL)
+      return PP_SCATTER_FORM_COLUMN;
+    return f32 ? PP_SCATTER_FORM_ATOMICS : rest;
+  }
+  if (d.op == PP_SCATTER_INTERPOLATE && k.interp != 1 && k.interp != 3 && (size_t)d.Nd * sizeof(double) <= kColumnLds &&
+      (k.interp == 2 || d.P / 3 >= 2048))
+    return PP_SCATTER_FORM_COLUMN;   // enough points per column to pay for zeroing and flushing it
+  return rest;
+}
+
+template <bool VEC, typename T>
+int launch_group_column(const ScatterDesc& d, const T* src, const int* dst, T* out, hipStream_t s) {
+  static pp::DeviceFlags ok;
+  const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, VEC, T>, kColumnLds, ok);
+  if (e != hipSuccess) return (int)e;
+  const int nsplit = (d.Nd + kW64 - 1) / kW64;
+  const long long wgs = 8LL * ((d.B + 7) / 8) * d.C * nsplit;
+  const int W = nsplit == 1 ? d.Nd : kW64;
+  // overwrite: the column form writes every element once (no read of the output, no fill in front of it: 2 x 256 MB
+  // less traffic at config 4)
+  group_points_grad_lds64_kernel<8, VEC, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double), s>>>(
+      src, dst, out, d.B, d.C, d.Nd, d.P, d.src_bstride, nsplit, W, d.write ? 1 : 0);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+template <typename T>
+int launch_column(const ScatterDesc& d, const T* src, const int* dst, const float* weight, T* out, hipStream_t s) {
+  if (d.op == PP_SCATTER_GROUP) {
+    // 16-byte index quads beside quads of T (16 or 8 bytes)
+    const bool vec = (uintptr_t)src % (4 * sizeof(T)) == 0 && (uintptr_t)dst % 16 == 0 && d.P % 4 == 0 &&
+                     d.src_bstride % 4 == 0;
+    return vec ? launch_group_column<true>(d, src, dst, out, s) : launch_group_column<false>(d, src, dst, out, s);
+  }
+  const int N = (int)(d.P / 3), M = d.Nd;
+  const size_t col = (size_t)M * sizeof(double);
+  if (d.C >= 4 && 4 * col <= kColumnLds)
+    return launch_three_interpolate_grad_lds64<4>(src, dst, weight, out, d.B, d.C, N, M, s);
+  if (d.C >= 2 && 2 * col <= kColumnLds)
+    return launch_three_interpolate_grad_lds64<2>(src, dst, weight, out, d.B, d.C, N, M, s);
+  return launch_three_interpolate_grad_lds64<1>(src, dst, weight, out, d.B, d.C, N, M, s);
+}
+
+int launch_atomics(const ScatterDesc& d, const float* src, const int* dst, const float* weight, float* out,
+                   hipStream_t s) {
+  const long long sources = d.P / d.R;
+  const long long cols = (sources + 255) / 256;
+  const int cpb = pick_c_per_block(cols, d.B, d.C);
+  const long long gy = (d.C + cpb - 1) / cpb;
+  if (!grid_ok(cols, gy, d.B)) return PP_EINVAL;
+  const dim3 grid((unsigned)cols, (unsigned)gy, (unsigned)d.B), block(256);
+  if (d.op == PP_SCATTER_GATHER)
+    gather_bwd_kernel<<<grid, block, 0, s>>>(src, dst, out, d.C, d.Nd, (int)sources, cpb);
+  else if (d.op == PP_SCATTER_GROUP)
+    group_points_grad_kernel<<<grid, block, 0, s>>>(src, dst, out, d.C, d.Nd, d.P, cpb, d.src_bstride);
+  else
+    three_interpolate_grad_kernel<<<grid, block, 0, s>>>(src, dst, weight, out, d.C, (int)sources, d.Nd, cpb);
+  PP_RETURN_IF_LAUNCH_FAILED();
+  return PP_OK;
+}
+
+// Return codes for degenerate arguments differ by the entry's kind, as the entries always had them: a negative size is
+// PP_EINVAL before any pointer is looked at; the accumulating entries (the reference's contract) serve B, C or the
+// sources being 0 and reject work without destinations; the writing ones serve B, C or the destinations being 0 and
+// zero the output when there are no sources; the fp32 ordered ones serve any zero size.
+template <typename T>
+int scatter_run(ScatterDesc d, const T* src, const int* dst, const float* weight, T* out, void* stream) {
+  constexpr bool kF32 = std::is_same<T, float>::value;
+  d.elem_bytes = (int)sizeof(T);
+  hipStream_t s = (hipStream_t)stream;
+  if (d.B < 0 || d.C < 0 || d.P < 0 || d.Nd < 0) return PP_EINVAL;
+  const bool short_stride = d.src_bstride < (long long)d.C * (d.P / d.R);
+  const size_t out_bytes = (size_t)d.B * d.C * d.Nd * sizeof(T);
+  if (d.write) {
+    if (d.B == 0 || d.C == 0 || d.Nd == 0) return PP_OK;
+    if (!out) return PP_EINVAL;
+    if (d.P == 0) return (int)pp::fill_bytes(out, 0, out_bytes, s);   // (+0 in all three types)
+  } else if (d.ordered) {
+    if (d.B == 0 || d.C == 0 || d.Nd == 0 || d.P == 0) return PP_OK;
+  } else {
+    if (short_stride) return PP_EINVAL;
+    if (d.B == 0 || d.C == 0 || d.P == 0) return PP_OK;
+  }
+  if (!src || !dst || !out || (d.weighted && !weight) || d.Nd == 0 || short_stride) return PP_EINVAL;
+  const int form = scatter_plan(d, {g_group_grad_variant, g_interp_grad_variant, g_scatter_mode});
+  if (form == PP_SCATTER_FORM_NONE) return PP_ENOTSUP;
+  const bool writes = !kF32 || (form == PP_SCATTER_FORM_COLUMN && d.op == PP_SCATTER_GROUP);
+  if (d.write && !writes) {   // (pp::fill_bytes: not hipMemsetAsync)
+    const hipError_t e = pp::fill_bytes(out, 0, out_bytes, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  if (form == PP_SCATTER_FORM_COLUMN) return launch_column(d, src, dst, weight, out, s);
+  if constexpr (kF32)
+    if (form == PP_SCATTER_FORM_ATOMICS) return launch_atomics(d, src, dst, weight, out, s);
+  return pp::ssa_run(src, dst, d.weighted ? weight : nullptr, out, d.B, d.C, d.P, d.R, d.Nd, d.src_bstride, d.ws, s,
+                     form == PP_SCATTER_FORM_ORDERED);
+}
+
+constexpr bool kAccumulate = false, kWrite = true;
+
+}  // namespace
+
+extern "C" int pp_debug_scatter_plan(int op, int elem_bytes, int write, int ordered, int B, int C, long long sources,
+                                     int destinations, size_t workspace_bytes) {
+  if (op < PP_SCATTER_GATHER || op > PP_SCATTER_INTERPOLATE || (elem_bytes != 2 && elem_bytes != 4)) return -1;
+  if (B <= 0 || C <= 0 || sources <= 0 || sources > 0x7fffffffLL || destinations <= 0) return -1;
+  ScatterDesc d = op == PP_SCATTER_GATHER  ? gather_desc(B, C, destinations, (int)sources)
+                  : op == PP_SCATTER_GROUP ? group_desc(B, C, destinations, (int)sources, 1, C * sources)
+                                           : interp_desc(B, C, (int)sources, destinations);
+  d.elem_bytes = elem_bytes, d.write = write != 0, d.ordered = ordered != 0, d.ws_bytes = workspace_bytes;
+  return scatter_plan(d, {g_group_grad_variant, g_interp_grad_variant, g_scatter_mode});
+}
+
+// ---- fp32, accumulating into the caller's (zeroed) output: the reference's contract ----
+extern "C" int pp_gather_backward_f32(const float* grad_out, const int* idx, float* grad_points,
+                                      int B, int C, int N, int M, void* stream) {
+  return scatter_run(gather_desc(B, C, N, M), grad_out, idx, nullptr, grad_points, stream);
+}
+extern "C" int pp_group_points_grad_f32(const float* grad_out, const int* idx, float* grad_points,
+                                        int B, int C, int N, int npoint, int nsample, void* stream) {
+  return scatter_run(group_desc(B, C, N, npoint, nsample, (long long)C * npoint * nsample), grad_out, idx, nullptr,
+                     grad_points, stream);
+}
+extern "C" int pp_group_points_grad_strided_f32(const float* grad_out, const int* idx, float* grad_points,
+                                                int B, int C, int N, int npoint, int nsample,
+                                                long long grad_out_batch_stride, void* stream) {
+  return scatter_run(group_desc(B, C, N, npoint, nsample, grad_out_batch_stride), grad_out, idx, nullptr, grad_points,
+                     stream);
+}
+extern "C" int pp_three_interpolate_grad_f32(const float* grad_out, const int* idx, const float* weight,
+                                             float* grad_points, int B, int C, int N, int M, void* stream) {
+  return scatter_run(interp_desc(B, C, N, M), grad_out, idx, weight, grad_points, stream);
+}
+
+// ---- the same with a caller-provided workspace (pp_scatter_workspace_bytes), which admits the sorted form ----
+extern "C" int pp_gather_backward_ws_f32(const float* grad_out, const int* idx, float* grad_points, int B,
+                                         int C, int N, int M, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  return scatter_run(gather_desc(B, C, N, M).with(kAccumulate, false, workspace, workspace_bytes), grad_out, idx,
+                     nullptr, grad_points, stream);
+}
 extern "C" int pp_group_points_grad_ws_f32(const float* grad_out, const int* idx, float* grad_points, int B,
                                            int C, int N, int npoint, int nsample,
                                            long long grad_out_batch_stride, void* workspace,
                                            size_t workspace_bytes, void* stream) {
-  const long long P = (long long)npoint * nsample;
-  // With many triples per destination (16 at config 4) the sorted form moves more bytes through each
-  // CU than the LDS-column form spends on its slow ds_add_f32 (6.3 vs 5.8 ms there); it wins when the
-  // lists are short.
-  if (B > 0 && C > 0 && P > 0 && grad_out && idx && grad_points && N > 0 && P <= 4LL * N &&
-      grad_out_batch_stride >= (long long)C * P && scatter_ok(B, C, P, 1, N, 0, workspace, workspace_bytes))
-    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, grad_out_batch_stride, workspace,
-                       (hipStream_t)stream, false);
-  return pp_group_points_grad_strided_f32(grad_out, idx, grad_points, B, C, N, npoint, nsample,
-                                          grad_out_batch_stride, stream);
+  return scatter_run(group_desc(B, C, N, npoint, nsample, grad_out_batch_stride)
+                         .with(kAccumulate, false, workspace, workspace_bytes),
+                     grad_out, idx, nullptr, grad_points, stream);
+}
+extern "C" int pp_three_interpolate_grad_ws_f32(const float* grad_out, const int* idx, const float* weight,
+                                                float* grad_points, int B, int C, int N, int M,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
+  return scatter_run(interp_desc(B, C, N, M).with(kAccumulate, false, workspace, workspace_bytes), grad_out, idx,
+                     weight, grad_points, stream);
 }
 
-// the same with grad_points WRITTEN, not accumulated into: the caller passes uninitialised memory (the Python shim:
-// torch.empty instead of torch.zeros)
+// ---- grad_points WRITTEN, not accumulated into: the caller passes uninitialised memory (the Python shim:
+// torch.empty instead of torch.zeros) ----
 extern "C" int pp_group_points_grad_out_ws_f32(const float* grad_out, const int* idx, float* grad_points, int B,
                                                int C, int N, int npoint, int nsample,
                                                long long grad_out_batch_stride, void* workspace,
                                                size_t workspace_bytes, void* stream) {
-  const long long P = (long long)npoint * nsample;
-  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || N == 0) return PP_OK;
-  if (!grad_points) return PP_EINVAL;
-  if (P == 0) return zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
-  if (grad_out && idx && P <= 4LL * N && grad_out_batch_stride >= (long long)C * P &&
-      scatter_ok(B, C, P, 1, N, 0, workspace, workspace_bytes)) {  // the sorted form accumulates
-    const int e = zero_f32(grad_points, (size_t)B * C * N, (hipStream_t)stream);
-    if (e != PP_OK) return e;
-    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, grad_out_batch_stride, workspace,
-                       (hipStream_t)stream, false);
-  }
-  return group_points_grad_launch(grad_out, idx, grad_points, B, C, N, npoint, nsample, grad_out_batch_stride, stream,
-                                  true);
+  return scatter_run(group_desc(B, C, N, npoint, nsample, grad_out_batch_stride)
+                         .with(kWrite, false, workspace, workspace_bytes),
+                     grad_out, idx, nullptr, grad_points, stream);
 }
 
-extern "C" int pp_gather_backward_ws_f32(const float* grad_out, const int* idx, float* grad_points, int B,
-                                         int C, int N, int M, void* workspace, size_t workspace_bytes,
-                                         void* stream) {
-  if (B > 0 && C > 0 && M > 0 && N > 0 && grad_out && idx && grad_points &&
-      scatter_ok(B, C, M, 1, N, 0, workspace, workspace_bytes))
-    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, M, 1, N, (long long)C * M, workspace,
-                       (hipStream_t)stream, false);
-  return pp_gather_backward_f32(grad_out, idx, grad_points, B, C, N, M, stream);
+// ---- ORDERED (deterministic mode): selected by the Python / C++ host side when
+// torch.are_deterministic_algorithms_enabled().  PP_ENOTSUP when the problem does not fit the form (more than 20480
+// destinations per batch element, workspace too small): there is no deterministic substitute. ----
+extern "C" int pp_gather_backward_ordered_f32(const float* grad_out, const int* idx, float* grad_points, int B,
+                                              int C, int N, int M, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  return scatter_run(gather_desc(B, C, N, M).with(kAccumulate, true, workspace, workspace_bytes), grad_out, idx,
+                     nullptr, grad_points, stream);
 }
-
-extern "C" int pp_three_interpolate_grad_ws_f32(const float* grad_out, const int* idx, const float* weight,
-                                                float* grad_points, int B, int C, int N, int M,
-                                                void* workspace, size_t workspace_bytes, void* stream) {
-  // the LDS-column form (0.18 ms at B=32, C=128, N=16384, M=4096) beats the sorted form (0.55 ms)
-  // wherever its column fits
-  const bool columns = g_interp_grad_variant != 1 && g_interp_grad_variant != 3 &&
-                       (size_t)M * sizeof(double) <= 152 * 1024 && (g_interp_grad_variant == 2 || N >= 2048);
-  if (!columns && B > 0 && C > 0 && N > 0 && M > 0 && grad_out && idx && weight && grad_points &&
-      scatter_ok(B, C, 3LL * N, 3, M, 1, workspace, workspace_bytes))
-    return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, workspace,
-                       (hipStream_t)stream, false);
-  return pp_three_interpolate_grad_f32(grad_out, idx, weight, grad_points, B, C, N, M, stream);
-}
-
-// ---- ORDERED scatter-add backwards (deterministic mode) ------------------------------------------------
-// The sorted-triples form of scatter.hip with every destination's terms added in ascending source order: no
-// atomics on floating-point data, results identical from run to run and identical, bit for bit, to a
-// sequential loop in the order of the reference's launch (the CPU oracle).  Selected by the Python / C++ host
-// side when torch.are_deterministic_algorithms_enabled().  PP_ENOTSUP when the problem does not fit the form
-// (more than 20480 destinations per batch element, workspace too small): there is no deterministic substitute.
-static bool ordered_ok(int B, long long P, int R, int Nd, int weighted, const void* ws, size_t bytes) {
-  const size_t need = pp::ssa_workspace_bytes(B, P, R, Nd, weighted != 0);
-  return ws && need != 0 && bytes >= need;
-}
-
 extern "C" int pp_group_points_grad_ordered_f32(const float* grad_out, const int* idx, float* grad_points, int B,
                                                 int C, int N, int npoint, int nsample,
                                                 long long grad_out_batch_stride, void* workspace,
                                                 size_t workspace_bytes, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
-  const long long P = (long long)npoint * nsample;
-  if (B == 0 || C == 0 || N == 0 || P == 0) return PP_OK;
-  if (!grad_out || !idx || !grad_points || grad_out_batch_stride < (long long)C * P) return PP_EINVAL;
-  if (!ordered_ok(B, P, 1, N, 0, workspace, workspace_bytes)) return PP_ENOTSUP;
-  return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, grad_out_batch_stride, workspace,
-                     (hipStream_t)stream, true);
+  return scatter_run(group_desc(B, C, N, npoint, nsample, grad_out_batch_stride)
+                         .with(kAccumulate, true, workspace, workspace_bytes),
+                     grad_out, idx, nullptr, grad_points, stream);
 }
-
-extern "C" int pp_gather_backward_ordered_f32(const float* grad_out, const int* idx, float* grad_points, int B,
-                                              int C, int N, int M, void* workspace, size_t workspace_bytes,
-                                              void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || N == 0 || M == 0) return PP_OK;
-  if (!grad_out || !idx || !grad_points) return PP_EINVAL;
-  if (!ordered_ok(B, M, 1, N, 0, workspace, workspace_bytes)) return PP_ENOTSUP;
-  return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, M, 1, N, (long long)C * M, workspace,
-                     (hipStream_t)stream, true);
-}
-
 extern "C" int pp_three_interpolate_grad_ordered_f32(const float* grad_out, const int* idx, const float* weight,
                                                      float* grad_points, int B, int C, int N, int M,
                                                      void* workspace, size_t workspace_bytes, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || N == 0 || M == 0) return PP_OK;
-  if (!grad_out || !idx || !weight || !grad_points) return PP_EINVAL;
-  if (!ordered_ok(B, 3LL * N, 3, M, 1, workspace, workspace_bytes)) return PP_ENOTSUP;
-  return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, workspace,
-                     (hipStream_t)stream, true);
+  return scatter_run(interp_desc(B, C, N, M).with(kAccumulate, true, workspace, workspace_bytes), grad_out, idx,
+                     weight, grad_points, stream);
 }
+
+// ---- 16-bit features: grad_points WRITTEN and rounded once; `ordered` is an argument; PP_ENOTSUP where no atomic-free
+// form serves the shape (the caller widens and takes the fp32 entry) ----
+#define PP_SCATTER_B16(SUFFIX, T)                                                                                     \
+  extern "C" int pp_gather_backward_out_ws_##SUFFIX(const void* grad_out, const int* idx, void* grad_points, int B,  \
+                                                    int C, int N, int M, void* workspace, size_t workspace_bytes,    \
+                                                    int ordered, void* stream) {                                     \
+    return scatter_run(gather_desc(B, C, N, M).with(kWrite, ordered != 0, workspace, workspace_bytes),               \
+                       (const T*)grad_out, idx, nullptr, (T*)grad_points, stream);                                   \
+  }                                                                                                                   \
+  extern "C" int pp_group_points_grad_out_ws_##SUFFIX(const void* grad_out, const int* idx, void* grad_points, int B, \
+                                                      int C, int N, int npoint, int nsample,                         \
+                                                      long long grad_out_batch_stride, void* workspace,              \
+                                                      size_t workspace_bytes, int ordered, void* stream) {           \
+    return scatter_run(group_desc(B, C, N, npoint, nsample, grad_out_batch_stride)                                   \
+                           .with(kWrite, ordered != 0, workspace, workspace_bytes),                                  \
+                       (const T*)grad_out, idx, nullptr, (T*)grad_points, stream);                                   \
+  }                                                                                                                   \
+  extern "C" int pp_three_interpolate_grad_out_ws_##SUFFIX(const void* grad_out, const int* idx, const float* weight, \
+                                                           void* grad_points, int B, int C, int N, int M,            \
+                                                           void* workspace, size_t workspace_bytes, int ordered,     \
+                                                           void* stream) {                                           \
+    return scatter_run(interp_desc(B, C, N, M).with(kWrite, ordered != 0, workspace, workspace_bytes),               \
+                       (const T*)grad_out, idx, weight, (T*)grad_points, stream);                                    \
+  }
+PP_SCATTER_B16(f16, pp::f16)
+PP_SCATTER_B16(bf16, pp::bf16)
+#undef PP_SCATTER_B16
 
 // ================================================================================================
 // 16-bit features (DESIGN.md §4 "16-bit features"): gather_points, group_points and three_interpolate on fp16 / bf16
@@ -1932,96 +1984,6 @@ int three_interpolate_b16(const T* points, const int* idx, const float* weight, 
   return PP_OK;
 }
 
-int zero_b16(void* p, size_t n, hipStream_t s) { return (int)pp::fill_bytes(p, 0, n * 2, s); }  // +0 in both types
-
-template <typename T>
-int gather_backward_out_b16(const T* grad_out, const int* idx, T* grad_points, int B, int C, int N, int M,
-                            void* ws, size_t ws_bytes, int ordered, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || N == 0) return PP_OK;
-  if (!grad_points) return PP_EINVAL;
-  if (M == 0) return zero_b16(grad_points, (size_t)B * C * N, (hipStream_t)stream);
-  if (!grad_out || !idx) return PP_EINVAL;
-  if (!ordered_ok(B, M, 1, N, 0, ws, ws_bytes) || (!ordered && g_scatter_mode == 1)) return PP_ENOTSUP;
-  return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, M, 1, N, (long long)C * M, ws, (hipStream_t)stream,
-                     ordered != 0);
-}
-
-template <typename T>
-int group_points_grad_out_b16(const T* grad_out, const int* idx, T* grad_points, int B, int C, int N, int npoint,
-                              int nsample, long long gbs, void* ws, size_t ws_bytes, int ordered, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
-  const long long P = (long long)npoint * nsample;
-  if (B == 0 || C == 0 || N == 0) return PP_OK;
-  if (!grad_points) return PP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (P == 0) return zero_b16(grad_points, (size_t)B * C * N, s);
-  if (!grad_out || !idx || gbs < (long long)C * P) return PP_EINVAL;
-  const bool sorted_ok = ordered_ok(B, P, 1, N, 0, ws, ws_bytes);
-  if (ordered) {
-    if (!sorted_ok) return PP_ENOTSUP;
-    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, gbs, ws, s, true);
-  }
-  const int gv = g_group_grad_variant;
-  constexpr int kW64 = 152 * 1024 / 8;  // destinations per workgroup with a double column
-  const int nsplit = (N + kW64 - 1) / kW64;
-  const long long wgs = 8LL * ((B + 7) / 8) * C * nsplit;
-  const bool columns = gv != 1 && nsplit <= 16 && wgs <= 0x7fffffffLL && (gv == 2 || P >= 4096);
-  const bool sorted = sorted_ok && g_scatter_mode != 1;
-  // the fp32 dispatch's preference: short lists (P <= 4 N) of a problem large enough to pay for the sort go to the
-  // sorted form; otherwise the double column; the sorted form again where no column applies
-  if (sorted && gv != 2 && (!columns || (P <= 4LL * N && (long long)B * P * C >= (1LL << 20))))
-    return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, gbs, ws, s, false);
-  if (columns) {
-    const int W = nsplit == 1 ? N : kW64;
-    const bool vec = (uintptr_t)grad_out % 8 == 0 && (uintptr_t)idx % 16 == 0 && P % 4 == 0 && gbs % 4 == 0;
-    static pp::DeviceFlags okv, oks;
-    if (vec) {
-      const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, true, T>, 152 * 1024, okv);
-      if (e != hipSuccess) return (int)e;
-      group_points_grad_lds64_kernel<8, true, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double), s>>>(
-          grad_out, idx, grad_points, B, C, N, P, gbs, nsplit, W, 1);
-    } else {
-      const hipError_t e = pp::allow_big_lds(group_points_grad_lds64_kernel<8, false, T>, 152 * 1024, oks);
-      if (e != hipSuccess) return (int)e;
-      group_points_grad_lds64_kernel<8, false, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)W * sizeof(double), s>>>(
-          grad_out, idx, grad_points, B, C, N, P, gbs, nsplit, W, 1);
-    }
-    PP_RETURN_IF_LAUNCH_FAILED();
-    return PP_OK;
-  }
-  if (sorted) return pp::ssa_run(grad_out, idx, nullptr, grad_points, B, C, P, 1, N, gbs, ws, s, false);
-  return PP_ENOTSUP;
-}
-
-template <typename T>
-int three_interpolate_grad_out_b16(const T* grad_out, const int* idx, const float* weight, T* grad_points, int B,
-                                   int C, int N, int M, void* ws, size_t ws_bytes, int ordered, void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || M == 0) return PP_OK;
-  if (!grad_points) return PP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (N == 0) return zero_b16(grad_points, (size_t)B * C * M, s);
-  if (!grad_out || !idx || !weight) return PP_EINVAL;
-  const bool sorted_ok = ordered_ok(B, 3LL * N, 3, M, 1, ws, ws_bytes);
-  if (ordered) {
-    if (!sorted_ok) return PP_ENOTSUP;
-    return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, ws, s, true);
-  }
-  const int gv = g_interp_grad_variant;
-  const size_t col = (size_t)M * sizeof(double);
-  if (gv != 1 && gv != 3 && col <= 152 * 1024 && (gv == 2 || N >= 2048)) {
-    if (C >= 4 && 4 * col <= 152 * 1024)
-      return launch_three_interpolate_grad_lds64<4>(grad_out, idx, weight, grad_points, B, C, N, M, s);
-    if (C >= 2 && 2 * col <= 152 * 1024)
-      return launch_three_interpolate_grad_lds64<2>(grad_out, idx, weight, grad_points, B, C, N, M, s);
-    return launch_three_interpolate_grad_lds64<1>(grad_out, idx, weight, grad_points, B, C, N, M, s);
-  }
-  if (sorted_ok && g_scatter_mode != 1)
-    return pp::ssa_run(grad_out, idx, weight, grad_points, B, C, 3LL * N, 3, M, (long long)C * N, ws, s, false);
-  return PP_ENOTSUP;
-}
-
 }  // namespace
 
 extern "C" int pp_gather_forward_b16(const void* points_, const int* idx, void* out_, int B, int C, int N, int M,
@@ -2126,43 +2088,4 @@ extern "C" int pp_three_interpolate_f16(const void* points, const int* idx, cons
 extern "C" int pp_three_interpolate_bf16(const void* points, const int* idx, const float* weight, void* out, int B,
                                          int C, int M, int N, void* stream) {
   return three_interpolate_b16((const pp::bf16*)points, idx, weight, (pp::bf16*)out, B, C, M, N, stream);
-}
-
-extern "C" int pp_gather_backward_out_ws_f16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
-                                             int N, int M, void* workspace, size_t workspace_bytes, int ordered,
-                                             void* stream) {
-  return gather_backward_out_b16((const pp::f16*)grad_out, idx, (pp::f16*)grad_points, B, C, N, M, workspace,
-                                 workspace_bytes, ordered, stream);
-}
-extern "C" int pp_gather_backward_out_ws_bf16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
-                                              int N, int M, void* workspace, size_t workspace_bytes, int ordered,
-                                              void* stream) {
-  return gather_backward_out_b16((const pp::bf16*)grad_out, idx, (pp::bf16*)grad_points, B, C, N, M, workspace,
-                                 workspace_bytes, ordered, stream);
-}
-
-extern "C" int pp_group_points_grad_out_ws_f16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
-                                               int N, int npoint, int nsample, long long grad_out_batch_stride,
-                                               void* workspace, size_t workspace_bytes, int ordered, void* stream) {
-  return group_points_grad_out_b16((const pp::f16*)grad_out, idx, (pp::f16*)grad_points, B, C, N, npoint, nsample,
-                                   grad_out_batch_stride, workspace, workspace_bytes, ordered, stream);
-}
-extern "C" int pp_group_points_grad_out_ws_bf16(const void* grad_out, const int* idx, void* grad_points, int B, int C,
-                                                int N, int npoint, int nsample, long long grad_out_batch_stride,
-                                                void* workspace, size_t workspace_bytes, int ordered, void* stream) {
-  return group_points_grad_out_b16((const pp::bf16*)grad_out, idx, (pp::bf16*)grad_points, B, C, N, npoint, nsample,
-                                   grad_out_batch_stride, workspace, workspace_bytes, ordered, stream);
-}
-
-extern "C" int pp_three_interpolate_grad_out_ws_f16(const void* grad_out, const int* idx, const float* weight,
-                                                    void* grad_points, int B, int C, int N, int M, void* workspace,
-                                                    size_t workspace_bytes, int ordered, void* stream) {
-  return three_interpolate_grad_out_b16((const pp::f16*)grad_out, idx, weight, (pp::f16*)grad_points, B, C, N, M,
-                                        workspace, workspace_bytes, ordered, stream);
-}
-extern "C" int pp_three_interpolate_grad_out_ws_bf16(const void* grad_out, const int* idx, const float* weight,
-                                                     void* grad_points, int B, int C, int N, int M, void* workspace,
-                                                     size_t workspace_bytes, int ordered, void* stream) {
-  return three_interpolate_grad_out_b16((const pp::bf16*)grad_out, idx, weight, (pp::bf16*)grad_points, B, C, N, M,
-                                        workspace, workspace_bytes, ordered, stream);
 }

@@ -41,6 +41,22 @@ def knob(name, value):
         set_knob(name, 0)
 
 
+# the scatter-add backwards' operators and forms (include/pp_hip_debug.h: pp_debug_scatter_plan)
+GATHER, GROUP, INTERP = 0, 1, 2
+NONE, ATOMICS, COLUMN, SORTED, ORDERED = 0, 1, 2, 3, 4
+
+
+def assert_plan(dtype, op, b, c, sources, destinations, form):
+    """the knobs as they stand select `form` for the shim's call on `dtype` tensors (with the workspace it passes)"""
+    per_source = 3 if op == INTERP else 1
+    ws = int(_lib.lib().pp_scatter_workspace_bytes(b, per_source * sources, destinations, per_source, int(op == INTERP)))
+    fn = _lib.lib().pp_debug_scatter_plan
+    fn.argtypes = [ctypes.c_int] * 6 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t]
+    fn.restype = ctypes.c_int
+    elem = 4 if dtype is torch.float32 else 2
+    assert fn(op, elem, int(elem == 2 or op == GROUP), 0, b, c, sources, destinations, ws) == form
+
+
 @contextlib.contextmanager
 def deterministic():
     before = torch.are_deterministic_algorithms_enabled()
@@ -240,12 +256,19 @@ def check_written(out, dst, n):
 
 
 GROUP_GRAD_SHAPES = [(2, 4, 1000, 64, 64), (2, 4, 1000, 241, 17), (2, 3, 7, 3, 5)]
+# the automatic forms (16-bit, fp32 reference): the column from 4096 positions; the last shape has 15, where 16-bit sorts
+# and fp32 -- too small to sort -- takes its atomics
+GROUP_GRAD_FORMS = {GROUP_GRAD_SHAPES[0]: (COLUMN, COLUMN), GROUP_GRAD_SHAPES[1]: (COLUMN, COLUMN),
+                    GROUP_GRAD_SHAPES[2]: (SORTED, ATOMICS)}
 
 
 @pytest.mark.parametrize("dtype", TYPES, ids=TYPE_IDS)
 @pytest.mark.parametrize("shape", GROUP_GRAD_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_group_points_grad(cuda, dtype, shape):
     n = shape[2]
+    plan = (GROUP, shape[0], shape[1], shape[3] * shape[4], n)
+    assert_plan(dtype, *plan, GROUP_GRAD_FORMS[shape][0])
+    assert_plan(torch.float32, *plan, GROUP_GRAD_FORMS[shape][1])
     grad_out, idx = group_grad_case(shape, dtype, cuda)
     ref = sampling.group_points_grad(grad_out.float(), idx, n).to(dtype)
     code, out = raw_group_grad(grad_out, idx, n)
@@ -254,6 +277,8 @@ def test_group_points_grad(cuda, dtype, shape):
     assert units_apart(out, ref) <= 1
     assert units_apart(sampling.group_points_grad(grad_out, idx, n), ref) <= 1
     with knob("group_points_grad_variant", 2):            # the double column, for the fp32 reference as well
+        assert_plan(dtype, *plan, COLUMN)
+        assert_plan(torch.float32, *plan, COLUMN)
         ref2 = sampling.group_points_grad(grad_out.float(), idx, n).to(dtype)
         code, out2 = raw_group_grad(grad_out, idx, n)
     assert code == 0
@@ -325,7 +350,12 @@ def test_three_interpolate_grad(cuda, dtype, shape, variant):
         check_written(out, idx, m)
         return out
 
+    # the form each id names, and the fp32 reference's: 100 points are too few for fp32 to sort -- its atomics
+    form16, form32 = {((2, 4, 2048, 512), 0): (COLUMN, COLUMN), ((2, 3, 100, 30), 0): (SORTED, ATOMICS),
+                      ((2, 3, 100, 30), 2): (COLUMN, COLUMN)}[(shape, variant)]
     with knob("three_interpolate_grad_variant", variant):
+        assert_plan(dtype, INTERP, b, c, n, m, form16)
+        assert_plan(torch.float32, INTERP, b, c, n, m, form32)
         out, ref = run(), fp32()
     if variant == 2 or shape[2] >= 2048:                  # the double columns: the fp32 operator's own bits
         assert torch.equal(bits(out), bits(ref))

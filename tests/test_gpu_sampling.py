@@ -463,10 +463,31 @@ def test_ball_query_grid_largest_rows(cuda, search):
 
 
 # --------------------------------------------------------------------------------- group points
+# the scatter-add backwards' operators and forms (include/pp_hip_debug.h: pp_debug_scatter_plan)
+GATHER, GROUP, INTERP = 0, 1, 2
+ATOMICS, COLUMN, SORTED = 1, 2, 3
+# form by group_grad_path: every shape with 4096 positions or more takes the column by itself (none is a short list of
+# a big problem, which alone would be sorted); below that the atomics, and the column only when forced
+CAC = {"auto": COLUMN, "global_atomics": ATOMICS, "lds_columns": COLUMN}
+AAC = {"auto": ATOMICS, "global_atomics": ATOMICS, "lds_columns": COLUMN}
+
+
+def assert_plan(op, b, c, sources, destinations, form, write=0):
+    """the knobs as they stand select `form` for the fp32 call the shim is about to make (with the workspace it passes)"""
+    import ctypes
+    from pytorch_points_amd import _lib
+    per_source = 3 if op == INTERP else 1
+    ws = int(_lib.lib().pp_scatter_workspace_bytes(b, per_source * sources, destinations, per_source, int(op == INTERP)))
+    fn = _lib.lib().pp_debug_scatter_plan
+    fn.argtypes = [ctypes.c_int] * 6 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_size_t]
+    fn.restype = ctypes.c_int
+    assert fn(op, 4, write, 0, b, c, sources, destinations, ws) == form
+
+
 @pytest.fixture(params=["auto", "global_atomics", "lds_columns"])
 def group_grad_path(request, cuda):
     """auto = sorted-triples scatter-add where it qualifies (scatter.hip); the others switch it off and
-    force global atomics or the LDS column in double (ds_add_f64)."""
+    force global atomics or the LDS column in double (ds_add_f64).  Each case states the form it gets (CAC / AAC)."""
     import ctypes
     from pytorch_points_amd import _lib
     setter = _lib.lib().pp_debug_set_group_points_grad_variant
@@ -520,7 +541,9 @@ def test_gather_forward_large(cuda, variant, b, c, n, m):
 
 @pytest.mark.parametrize("b,c,n,m", [(3, 40, 5000, 20001), (9, 16, 16384, 8192), (1, 130, 777, 40000)])
 def test_gather_backward_large(cuda, scatter_path, b, c, n, m):
+    """every shape has B M C >= 2^20 and N <= 20480: sorted unless the scatter mode forbids it, then the atomics"""
     from pytorch_points_amd._ext import sampling
+    assert_plan(GATHER, b, c, m, n, {"sorted": SORTED, "atomics": ATOMICS}[scatter_path])
     go = _t(S.normal(23, (b, c, m)), cuda)
     idx = _t((S.uniform01(24, (b, m)).reshape(b, m) * n).astype(np.int32), cuda)
     gp = torch.zeros(b, c, n, device=cuda)
@@ -549,10 +572,21 @@ def interp_grad_path(request, cuda):
     smode(0)
 
 
-@pytest.mark.parametrize("b,c,n,m", [(2, 33, 16384, 4096), (9, 8, 5001, 700), (1, 64, 40000, 20480), (3, 6, 3000, 9000),
-                                     (2, 3, 2500, 19456)])
+# the form by interp_grad_path (auto, global_atomics, lds_columns, sorted): the column wherever it fits; at M = 20480 it
+# does not (160 KiB), and the big problem is sorted even with the column forced; the last two are too small (B 3N C <
+# 2^20) for fp32 to sort, so "sorted" gets the atomics there
+INTERP_GRAD_FORMS = {(2, 33, 16384, 4096): (COLUMN, ATOMICS, COLUMN, SORTED),
+                     (9, 8, 5001, 700): (COLUMN, ATOMICS, COLUMN, SORTED),
+                     (1, 64, 40000, 20480): (SORTED, ATOMICS, SORTED, SORTED),
+                     (3, 6, 3000, 9000): (COLUMN, ATOMICS, COLUMN, ATOMICS),
+                     (2, 3, 2500, 19456): (COLUMN, ATOMICS, COLUMN, ATOMICS)}
+
+
+@pytest.mark.parametrize("b,c,n,m", list(INTERP_GRAD_FORMS))
 def test_three_interpolate_grad_large(cuda, interp_grad_path, b, c, n, m):
     from pytorch_points_amd._ext import sampling
+    forms = INTERP_GRAD_FORMS[(b, c, n, m)]
+    assert_plan(INTERP, b, c, n, m, forms[["auto", "global_atomics", "lds_columns", "sorted"].index(interp_grad_path)])
     go = _t(S.normal(25, (b, c, n)), cuda)
     idx = _t((S.uniform01(26, (b, n, 3)).reshape(b, n, 3) * m).astype(np.int32), cuda)
     w = _t(S.uniform01(27, (b, n, 3)).reshape(b, n, 3).astype(np.float32), cuda)
@@ -564,13 +598,17 @@ def test_three_interpolate_grad_large(cuda, interp_grad_path, b, c, n, m):
     assert torch.allclose(gp.double(), ref, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("b,c,n,npoint,ns", [(2, 8, 2048, 256, 16), (1, 3, 100, 7, 5), (2, 67, 500, 33, 12), (1, 1, 10, 1, 1),
-                                             (9, 4, 4096, 512, 32), (4, 16, 4096, 1024, 32), (3, 10, 5000, 700, 48),
-                                             # shapes without 16-byte alignment / rows beyond 64 KiB (4-byte LDS-staged forms)
-                                             (9, 5, 16383, 1024, 64), (2, 6, 20000, 4096, 64), (4, 7, 4096, 4095, 33),
-                                             (2, 5, 3000, 1023, 33), (5, 4, 30001, 999, 107)])
+GROUP_GRAD_FORMS = {(2, 8, 2048, 256, 16): CAC, (1, 3, 100, 7, 5): AAC, (2, 67, 500, 33, 12): AAC, (1, 1, 10, 1, 1): AAC,
+                    (9, 4, 4096, 512, 32): CAC, (4, 16, 4096, 1024, 32): CAC, (3, 10, 5000, 700, 48): CAC,
+                    # shapes without 16-byte alignment / rows beyond 64 KiB (4-byte LDS-staged forms)
+                    (9, 5, 16383, 1024, 64): CAC, (2, 6, 20000, 4096, 64): CAC, (4, 7, 4096, 4095, 33): CAC,
+                    (2, 5, 3000, 1023, 33): CAC, (5, 4, 30001, 999, 107): CAC}
+
+
+@pytest.mark.parametrize("b,c,n,npoint,ns", list(GROUP_GRAD_FORMS))
 def test_group_points_matches_torch_and_backward(cuda, group_grad_path, b, c, n, npoint, ns):
     from pytorch_points_amd.network.operations import grouping_operation
+    assert_plan(GROUP, b, c, npoint * ns, n, GROUP_GRAD_FORMS[(b, c, n, npoint, ns)][group_grad_path], write=1)
     f = _t(S.normal(40, (b, c, n)), cuda).requires_grad_(True)
     idx = _t((S.uniform01(41, (b, npoint, ns)).reshape(b, npoint, ns) * n).astype(np.int32), cuda)
     out = grouping_operation(f, idx)
@@ -594,6 +632,7 @@ def test_group_points_grad_ball_rows_and_split_columns(cuda, group_grad_path, b,
     consecutive indices, merged in registers by the double-column kernel), and clouds too large for
     one LDS column (n > 19456: the column is split into destination ranges)."""
     from pytorch_points_amd._ext import sampling
+    assert_plan(GROUP, b, c, npoint * ns, n, CAC[group_grad_path], write=1)   # (every shape has 4096 positions or more)
     x = S.unit_sphere(45, b, n)
     idx = sampling.ball_query(_t(np.ascontiguousarray(x[:, :npoint]), cuda), _t(x, cuda), r, ns)
     idx[:, 0, :] = n - 1                 # a whole row on the last destination
