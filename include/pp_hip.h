@@ -722,6 +722,28 @@ int pp_mesh_distance_backward_f32(const float* points, const float* vertices, co
                                   float* grad_points, int B, int N, int F, int P, int shared_topology, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- mesh winding numbers and signed distance --------------------------------------------------
+ * The winding number of a triangle mesh about every point of a cloud, every (point, triangle) pair walked, alone or
+ * in the same walk as pp_mesh_point_face_forward_f32's choice; contract in DESIGN.md "Mesh winding numbers and signed
+ * distance".  fp32 points (B,P,3); records (B,F,16) are pp_mesh_distance_records_f32's, 16-byte aligned.  Both entries
+ * return PP_EINVAL where B*F, B*P or 3F exceeds 2^31 - 1 or a size is negative, before any launch, and PP_OK without a
+ * launch (and without a write) where B, P or F is 0.
+ * The half solid angle of point p and triangle (a,b,c), fp32 with every operation rounded on its own, dot(x,y) =
+ *   (x0*y0 + x1*y1) + x2*y2: u = a-p, v = b-p, w = c-p, lu = sqrt(dot(u,u)), lv, lw likewise, x = cross(v,w) with
+ *   x0 = v1*w2 - v2*w1, x1 = v2*w0 - v0*w2, x2 = v0*w1 - v1*w0, det = dot(u,x),
+ *   den = (((lu*lv)*lw + dot(u,v)*lw) + dot(v,w)*lu) + dot(w,u)*lv, h = atan2f(det, den).
+ * Per point the halves of the faces f = 0, 1, ... whose validity word is not 0 are added in fp64 in that order from +0,
+ *   and winding = (float)(sum / (2 pi)), rounded once: +1 inside a closed mesh whose faces are oriented outwards, 0
+ *   outside, negated by flipping the faces, a fraction for an open mesh, NaN for a NaN point (with a valid face).
+ * pp_mesh_winding_forward_f32: winding (B,P).
+ * pp_mesh_signed_distance_forward_f32: winding (B,P) with the same bits, and dist (B,P), face (B,P) int64, bary (B,P,3)
+ *   with pp_mesh_point_face_forward_f32's bits, from one walk.
+ * No atomics: every output word is written once, identical on every run. */
+int pp_mesh_winding_forward_f32(const float* points, const float* records, float* winding, int B, int P, int F,
+                                void* stream);
+int pp_mesh_signed_distance_forward_f32(const float* points, const float* records, float* dist, long long* face,
+                                        float* bary, float* winding, int B, int P, int F, void* stream);
+
 /* ---- earth mover's distance ------------------------------------------------------------------
  * The approximate matching of Fan, Su and Guibas (2017) between fp32 clouds xyz1 (B,N,3) and xyz2 (B,M,3), every pair
  * walked in every round; contract in DESIGN.md "Earth mover's distance".  No counterpart in the reference.

@@ -133,6 +133,8 @@ SIGNATURES = {
     "pp_mesh_point_face_forward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pp_mesh_face_point_forward_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pp_mesh_distance_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _c_size_t, _P],
+    "pp_mesh_winding_forward_f32": [_P, _P, _P, _I, _I, _I, _P],
+    "pp_mesh_signed_distance_forward_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pp_emd_workspace_bytes": [_I, _I, _I],
     "pp_emd_match_f32": [_P, _P, _P, _P, _I, _I, _I, _P, _c_size_t, _P],
     "pp_emd_dense_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],

@@ -1,5 +1,6 @@
-// mesh_common.h -- the one device layer of the five mesh files (mesh_edges.hip, mesh_dihedral.hip, mesh_normals.hip,
-// mesh_sample.hip, mesh_distance.hip); bucket_lists.h itself knows nothing of meshes.
+// mesh_common.h -- the one device layer of the six mesh files (mesh_edges.hip, mesh_dihedral.hip, mesh_normals.hip,
+// mesh_sample.hip, mesh_distance.hip, mesh_winding.hip); bucket_lists.h itself knows nothing of meshes.  mesh_pair.h,
+// beside it, is the pair function that the last two share.
 //   sizes       mesh_build_ok (the builds' index words), mesh_sizes_ok (the steps' launches)
 //   rows        mesh_half_edge, mesh_face (a face's three indices and whether all are in range), mesh_row (b, i, tb of
 //               a (b,vertex) lane), mesh_slice (its clipped slice of a (N+1)-word start table)

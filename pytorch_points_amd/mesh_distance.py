@@ -308,48 +308,55 @@ class MeshDistance(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_dist, *_):
-        want_points, want_vertices = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if grad_dist is None or not (want_points or want_vertices):
-            return (None,) * 4
-        points, vertices, index, bary = ctx.saved_tensors
-        corners, per_face = ctx.corners, ctx.per_face
-        b, n, _ = vertices.shape
-        p, f = points.shape[1], corners.n_faces
-        if b == 0 or n == 0 or f == 0 or p == 0:
-            return (torch.zeros_like(points) if want_points else None,
-                    torch.zeros_like(vertices) if want_vertices else None, None, None)
-        dev = vertices.device
-        s = f if per_face else p
-        shared = int(corners.batch == 1)
-        grad_dist = grad_dist.contiguous()
-        grad_points = torch.empty_like(points) if want_points else None
-        grad_vertices = torch.empty_like(vertices) if want_vertices else None
-        vec = torch.empty(b, f, 3, dtype=torch.float32, device=dev) if per_face and want_points else None
-        neg = torch.empty(b, s, 3, dtype=torch.float32, device=dev) if want_vertices else None
-        face = torch.empty(b, f, dtype=torch.int64, device=dev) if per_face and want_vertices else None
-        opt = lambda t: None if t is None else _lib.ptr(t)   # noqa: E731
-        lib = _lib.lib()
-        with _lib.on_device(dev) as stream:
-            if per_face:
-                wsp, nbytes, ws = _topology.workspace(dev, b, p, f) if want_points else (None, 0, None)
-                _lib.check(lib.pp_mesh_distance_backward_f32(
-                    _lib.ptr(points), _lib.ptr(vertices), _lib.ptr(corners.faces), None, _lib.ptr(index),
-                    _lib.ptr(bary), _lib.ptr(grad_dist), opt(vec), opt(neg), opt(face), opt(grad_points), b, n, f, p,
-                    shared, wsp, nbytes, stream), "mesh_distance backward")
-            else:
-                face = index
-                _lib.check(lib.pp_mesh_distance_backward_f32(
-                    _lib.ptr(points), _lib.ptr(vertices), _lib.ptr(corners.faces), _lib.ptr(index), None,
-                    _lib.ptr(bary), _lib.ptr(grad_dist), opt(grad_points), opt(neg), None, None, b, n, f, p, shared,
-                    None, 0, stream), "mesh_distance backward")
-            if want_vertices:
-                scratch = torch.empty(9 * b * f, dtype=torch.float32, device=dev)
-                wsp, nbytes, ws = _topology.workspace(dev, b, f, s)
-                _lib.check(lib.pp_mesh_sample_backward_f32(
-                    _lib.ptr(vertices), _lib.ptr(corners.faces), _lib.ptr(corners.start), _lib.ptr(corners.nbr),
-                    _lib.ptr(corners.codes), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(neg), None, _lib.ptr(scratch),
-                    _lib.ptr(grad_vertices), b, n, f, s, shared, wsp, nbytes, stream), "mesh_distance vertex gather")
-        return grad_points, grad_vertices, None, None
+        return _distance_backward(ctx, grad_dist) + (None, None)
+
+
+def _distance_backward(ctx, grad_dist):
+    """``(grad_points, grad_vertices)`` of ``dist`` at the chosen ``(index, bary)``, for a context that saved ``(points,
+    vertices, index, bary)`` and holds ``corners`` and ``per_face``: ``MeshDistance``'s backward, and that of
+    ``mesh_winding.MeshSignedDistance``, whose fused forward makes the same choice."""
+    want_points, want_vertices = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if grad_dist is None or not (want_points or want_vertices):
+        return None, None
+    points, vertices, index, bary = ctx.saved_tensors
+    corners, per_face = ctx.corners, ctx.per_face
+    b, n, _ = vertices.shape
+    p, f = points.shape[1], corners.n_faces
+    if b == 0 or n == 0 or f == 0 or p == 0:
+        return (torch.zeros_like(points) if want_points else None,
+                torch.zeros_like(vertices) if want_vertices else None)
+    dev = vertices.device
+    s = f if per_face else p
+    shared = int(corners.batch == 1)
+    grad_dist = grad_dist.contiguous()
+    grad_points = torch.empty_like(points) if want_points else None
+    grad_vertices = torch.empty_like(vertices) if want_vertices else None
+    vec = torch.empty(b, f, 3, dtype=torch.float32, device=dev) if per_face and want_points else None
+    neg = torch.empty(b, s, 3, dtype=torch.float32, device=dev) if want_vertices else None
+    face = torch.empty(b, f, dtype=torch.int64, device=dev) if per_face and want_vertices else None
+    opt = lambda t: None if t is None else _lib.ptr(t)   # noqa: E731
+    lib = _lib.lib()
+    with _lib.on_device(dev) as stream:
+        if per_face:
+            wsp, nbytes, ws = _topology.workspace(dev, b, p, f) if want_points else (None, 0, None)
+            _lib.check(lib.pp_mesh_distance_backward_f32(
+                _lib.ptr(points), _lib.ptr(vertices), _lib.ptr(corners.faces), None, _lib.ptr(index),
+                _lib.ptr(bary), _lib.ptr(grad_dist), opt(vec), opt(neg), opt(face), opt(grad_points), b, n, f, p,
+                shared, wsp, nbytes, stream), "mesh_distance backward")
+        else:
+            face = index
+            _lib.check(lib.pp_mesh_distance_backward_f32(
+                _lib.ptr(points), _lib.ptr(vertices), _lib.ptr(corners.faces), _lib.ptr(index), None,
+                _lib.ptr(bary), _lib.ptr(grad_dist), opt(grad_points), opt(neg), None, None, b, n, f, p, shared,
+                None, 0, stream), "mesh_distance backward")
+        if want_vertices:
+            scratch = torch.empty(9 * b * f, dtype=torch.float32, device=dev)
+            wsp, nbytes, ws = _topology.workspace(dev, b, f, s)
+            _lib.check(lib.pp_mesh_sample_backward_f32(
+                _lib.ptr(vertices), _lib.ptr(corners.faces), _lib.ptr(corners.start), _lib.ptr(corners.nbr),
+                _lib.ptr(corners.codes), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(neg), None, _lib.ptr(scratch),
+                _lib.ptr(grad_vertices), b, n, f, s, shared, wsp, nbytes, stream), "mesh_distance vertex gather")
+    return grad_points, grad_vertices
 
 
 def _hip_serves(points, vertices, corners):

@@ -11,7 +11,9 @@ get_edge_points (utils/geometry_utils.py:242-341: build_gemm, get_edge_points, g
 mesh_face_normals / mesh_vertex_normals (the reference has no vertex normals) with normalize_to_same_area
 (utils/geometry_utils.py:15-25), and the step from a mesh to points on its surface, which the reference lacks:
 mesh_sample_faces, mesh_interpolate and sample_points_from_meshes of pytorch_points_amd.mesh_sample under their names,
-and the exact distances point_face_distance and face_point_distance of pytorch_points_amd.mesh_distance.
+and the exact distances point_face_distance and face_point_distance of pytorch_points_amd.mesh_distance, with the
+side of the mesh from pytorch_points_amd.mesh_winding: mesh_winding_number, points_inside_mesh and
+point_mesh_signed_distance.
 Every function of the reference's geo_operations.py is served."""
 import collections
 
@@ -28,6 +30,8 @@ from .. import mesh_laplacian as _mesh_laplacian
 from .. import mesh_normals as _mesh_normals
 from ..mesh_distance import face_point_distance, point_face_distance  # noqa: F401 (no counterpart in the reference)
 from ..mesh_sample import mesh_interpolate, mesh_sample_faces, sample_points_from_meshes  # noqa: F401  (no counterpart)
+from ..mesh_winding import PointMeshSignedDistance, mesh_winding_number  # noqa: F401 (no counterpart in the reference)
+from ..mesh_winding import point_mesh_signed_distance, points_inside_mesh  # noqa: F401
 from .. import mvc as _mvc
 from .. import mvc2d as _mvc2d
 from .. import ops

@@ -21,6 +21,7 @@ from .. import mesh_laplacian as _mesh_laplacian
 from .. import mesh_normals as _mesh_normals
 from ..mesh_distance import PointMeshDistanceLoss  # noqa: F401 (no counterpart in the reference)
 from ..mesh_sample import SampledMeshChamferLoss  # noqa: F401  (no counterpart in the reference)
+from ..mesh_winding import MeshEnclosureLoss  # noqa: F401  (no counterpart in the reference)
 from .. import ops
 from .._ext import losses
 
