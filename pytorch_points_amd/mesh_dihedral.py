@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from . import _mesh_topology as _topology
 from . import mesh_edges as _mesh_edges
+from .mesh_normals import _cross
 
 _EPS = 1e-12                      # F.normalize's eps
 _LO, _HI = -1 + 1e-6, 1 - 1e-6    # the reference's clamp
@@ -143,8 +144,8 @@ def dihedral_composition(vertices, topo):
     table = torch.cat([torch.sort(table[..., :2], dim=-1)[0], torch.sort(table[..., 2:], dim=-1)[0]], dim=-1)
     table = table.clamp(0, n - 1).expand(b, -1, -1)
     p = [torch.gather(vertices, 1, table[:, :, k:k + 1].expand(-1, -1, 3)) for k in range(4)]
-    ua, oka = _unit(torch.cross(p[2] - p[0], p[1] - p[0], dim=-1))
-    ub, okb = _unit(torch.cross(p[3] - p[1], p[0] - p[1], dim=-1))
+    ua, oka = _unit(_cross(p[2] - p[0], p[1] - p[0]))        # (torch.cross may contract a*b - c*d: a wing with two
+    ub, okb = _unit(_cross(p[3] - p[1], p[0] - p[1]))        # equal vertices then has a normal of 1e-9, not 0)
     d = (ua[..., 0] * ub[..., 0] + ua[..., 1] * ub[..., 1]) + ua[..., 2] * ub[..., 2]
     d = torch.where(oka & okb, d, d.detach())
     angle = math.pi - torch.acos(d.clamp(_LO, _HI))
