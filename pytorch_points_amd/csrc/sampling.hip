@@ -20,6 +20,50 @@ namespace {
 using pp::dist3;
 
 // ------------------------------------------------------------------------------------------------
+// The copying forward kernels are templates on the element E: float, or any 2-byte element as u16 (a copy moves
+// bits, so one set of kernels serves fp16 and bf16: DESIGN.md §4 "16-bit features").  A lane of a vector form owns
+// L = 16 / sizeof(E) consecutive positions -- a quad of floats, an octet of u16: 16 bytes either way.  Indices stay
+// int32 and weights fp32; three_interpolate widens 16-bit features to fp32, runs the fp32 chain and rounds once.
+// Every guard of a vector form names its real requirement: a row (b, c) starts at byte (b * C + c) * N * sizeof(E),
+// 16-byte aligned only if N % L == 0, and the element-sized scalar forms serve any shape.
+// ------------------------------------------------------------------------------------------------
+typedef uint16_t u16;
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pack2(u16 lo, u16 hi) { return (unsigned)lo | ((unsigned)hi << 16); }
+// the L indices of a lane's positions: L / 4 16-byte loads
+template <int L>
+__device__ __forceinline__ void load_indices(int (&ii)[L], const int* __restrict__ p) {
+#pragma unroll
+  for (int j = 0; j < L; j += 4) {
+    const pp::i4 q = *reinterpret_cast<const pp::i4*>(p + j);
+    ii[j] = q.x; ii[j + 1] = q.y; ii[j + 2] = q.z; ii[j + 3] = q.w;
+  }
+}
+// 16 bytes of gathered elements s[ii[0]], s[ii[1]], ...
+__device__ __forceinline__ pp::f4 gather16(const float* s, const int (&ii)[4]) {
+  return pp::f4{s[ii[0]], s[ii[1]], s[ii[2]], s[ii[3]]};
+}
+__device__ __forceinline__ u4v gather16(const u16* s, const int (&ii)[8]) {
+  return u4v{pack2(s[ii[0]], s[ii[1]]), pack2(s[ii[2]], s[ii[3]]), pack2(s[ii[4]], s[ii[5]]), pack2(s[ii[6]], s[ii[7]])};
+}
+// the same from two index quads, for group_points_lds_b16_kernel alone: its quads come out of a `p < P ? load : 0`
+// select, and filled element by element into an int[8] behind that select the kernel compiles to another stream
+__device__ __forceinline__ u4v gather8(const u16* s, const pp::i4& a, const pp::i4& b) {
+  return u4v{pack2(s[a.x], s[a.y]), pack2(s[a.z], s[a.w]), pack2(s[b.x], s[b.y]), pack2(s[b.z], s[b.w])};
+}
+// a plain 16-byte store (fp32 through HIP's float4, the type group_points_kernel has always stored: hipcc addresses a
+// store of pp::f4 differently, and the kernels' instruction streams are held fixed)
+__device__ __forceinline__ void store16(float* p, const pp::f4& v) {
+  *reinterpret_cast<float4*>(p) = make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store16(u16* p, const u4v& v) { *reinterpret_cast<u4v*>(p) = v; }
+template <typename E, typename V16>  // the same past the caches
+__device__ __forceinline__ void store16_nt(E* p, const V16& v) {
+  __builtin_nontemporal_store(v, reinterpret_cast<V16*>(p));
+}
+
+// ------------------------------------------------------------------------------------------------
 // gather_points: out[b,c,m] = points[b,c,idx[b,m]]            (ref sampling_cuda.cu:9-25)
 // One thread per (b, m) column quad walks all channels: idx is read once, stores are contiguous.
 // ------------------------------------------------------------------------------------------------
@@ -42,12 +86,15 @@ __global__ __launch_bounds__(256) void gather_fwd_kernel(const E* __restrict__ p
 // and gathers from LDS, CPB channels in turn, the next row's loads in flight while this one is
 // gathered.  Reads 4 N bytes per row instead of one 64-byte sector per gathered element: the better
 // deal when N <= 16 M.  XCD mapping as group_points: idx of one batch element is read by one L2.
-template <int KR, bool VEC>
-__global__ __launch_bounds__(1024) void gather_fwd_lds_kernel(const float* __restrict__ points,
+// VEC is the fp32 vector form; the element-sized form (VEC = false) also serves E = u16.
+template <int KR, bool VEC, typename E = float>
+__global__ __launch_bounds__(1024) void gather_fwd_lds_kernel(const E* __restrict__ points,
                                                               const int* __restrict__ idx,
-                                                              float* __restrict__ out, int B, int C, int N,
+                                                              E* __restrict__ out, int B, int C, int N,
                                                               int M, int cpb, int groups) {
-  extern __shared__ __attribute__((aligned(16))) float s_grow[];
+  static_assert(!VEC || sizeof(E) == 4, "the 16-bit vector form is gather_fwd_lds_b16_kernel");
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_graw[];
+  E* s_grow = reinterpret_cast<E*>(s_graw);
   const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
   const int b = x + 8 * (y / groups);
   if (b >= B) return;
@@ -78,14 +125,43 @@ __global__ __launch_bounds__(1024) void gather_fwd_lds_kernel(const float* __res
         *reinterpret_cast<pp::f4*>(o + m) = r;
       }
     }
-  } else {  // no alignment assumed: 4-byte accesses, all coalesced
+  } else {  // no alignment assumed: element-sized accesses, all coalesced
     for (int c = c0; c < c1; ++c) {
       __syncthreads();
-      const float* __restrict__ row = points + ((size_t)b * C + c) * N;
+      const E* __restrict__ row = points + ((size_t)b * C + c) * N;
       for (int e = t; e < N; e += 1024) s_grow[e] = row[e];
       __syncthreads();
-      float* __restrict__ o = out + ((size_t)b * C + c) * M;
+      E* __restrict__ o = out + ((size_t)b * C + c) * M;
       for (int m = t; m < M; m += 1024) o[m] = s_grow[ib[m]];
+    }
+  }
+}
+
+// The 16-bit vector form (N % 8 == 0, M % 8 == 0, 16-byte aligned pointers): 16-byte row loads, two index quads and
+// one 16-byte store per lane.  Unlike the fp32 vector form it loads each row between the barriers: no next row in
+// flight through KR registers.
+__global__ __launch_bounds__(1024) void gather_fwd_lds_b16_kernel(const u16* __restrict__ points,
+                                                                  const int* __restrict__ idx,
+                                                                  u16* __restrict__ out, int B, int C, int N,
+                                                                  int M, int cpb, int groups) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_g16[];
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int b = x + 8 * (y / groups);
+  if (b >= B) return;
+  const int c0 = (y % groups) * cpb;
+  const int c1 = min(C, c0 + cpb);
+  const int t = threadIdx.x;
+  const int* __restrict__ ib = idx + (size_t)b * M;
+  for (int c = c0; c < c1; ++c) {
+    __syncthreads();  // the previous row has been gathered
+    const u16* __restrict__ row = points + ((size_t)b * C + c) * N;
+    u16* __restrict__ o = out + ((size_t)b * C + c) * M;
+    for (int e = t; e < (N >> 3); e += 1024) reinterpret_cast<u4v*>(s_g16)[e] = reinterpret_cast<const u4v*>(row)[e];
+    __syncthreads();
+    for (int m = t * 8; m < M; m += 8192) {
+      int ii[8];
+      load_indices(ii, ib + m);
+      store16(o + m, gather16(s_g16, ii));
     }
   }
 }
@@ -325,30 +401,28 @@ __global__ __launch_bounds__(256) void ball_query_split_kernel(const float* __re
 
 // ------------------------------------------------------------------------------------------------
 // group_points: out[b,c,j,k] = points[b,c,idx[b,j,k]]        (ref sampling_cuda.cu:447-467)
-// A thread owns 4 consecutive (j,k) positions: one 16-byte idx load, then per channel four
-// gathers and one 16-byte store.  The reference launches B blocks; this fills the chip.
+// VEC: a thread owns L consecutive (j,k) positions: 16-byte idx loads, then per channel L gathers and one 16-byte
+// store (P % L == 0, obs % L == 0, idx and out 16-byte aligned; the rows need no alignment: they are read one
+// element at a time); otherwise one position per thread.  The reference launches B blocks; this fills the chip.
 // ------------------------------------------------------------------------------------------------
-template <bool VEC4>
-__global__ __launch_bounds__(256) void group_points_kernel(const float* __restrict__ points,
+template <typename E, bool VEC>
+__global__ __launch_bounds__(256) void group_points_kernel(const E* __restrict__ points,
                                                            const int* __restrict__ idx,
-                                                           float* __restrict__ out, int C, int N,
+                                                           E* __restrict__ out, int C, int N,
                                                            long long P, int c_per_block, long long obs) {
+  constexpr int L = 16 / sizeof(E);
   const int b = blockIdx.z;
   const int c0 = blockIdx.y * c_per_block;
   const int c1 = min(C, c0 + c_per_block);
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (VEC4) {
-    const long long p = t * 4;
+  if (VEC) {
+    const long long p = t * L;
     if (p >= P) return;
-    const int4 ii = *reinterpret_cast<const int4*>(idx + (size_t)b * P + p);
+    int ii[L];
+    load_indices(ii, idx + (size_t)b * P + p);
     for (int c = c0; c < c1; ++c) {
-      const float* __restrict__ row = points + ((size_t)b * C + c) * N;
-      float4 v;
-      v.x = row[ii.x];
-      v.y = row[ii.y];
-      v.z = row[ii.z];
-      v.w = row[ii.w];
-      *reinterpret_cast<float4*>(out + (size_t)b * obs + (size_t)c * P + p) = v;
+      const auto r = gather16(points + ((size_t)b * C + c) * N, ii);
+      store16(out + (size_t)b * obs + (size_t)c * P + p, r);
     }
   } else {
     if (t >= P) return;
@@ -464,16 +538,19 @@ __global__ __launch_bounds__(512, 4) void group_points_lds_kernel(const float* _
 // buffer per 512-thread workgroup, two workgroups per CU: nothing overlaps inside a workgroup (DMA row c, wait,
 // barrier, gather + store, barrier); the two workgroups of a CU overlap each other and are not in step (0.89 against
 // 0.92 ms at config 4 for the 1024-thread ring of two buffers it replaced -- tools/archive/group_points_dma_ring_r2_r3
-// -- ; the stores alone, without any barrier, would take 0.75 ms).  Full chunks of 512 * 4 * V positions only.
+// -- ; the stores alone, without any barrier, would take 0.75 ms).  One wave instruction moves 1 KiB of the row.
+// Full chunks of 512 * L * V positions only: V index quads (fp32) or octets (16-bit) per thread.
 // ------------------------------------------------------------------------------------------------
 constexpr int kDma1Threads = 512;
-template <int V>
-__global__ __launch_bounds__(kDma1Threads) void group_points_dma1_kernel(const float* __restrict__ points,
+template <typename E, int V>
+__global__ __launch_bounds__(kDma1Threads) void group_points_dma1_kernel(const E* __restrict__ points,
                                                                          const int* __restrict__ idx,
-                                                                         float* __restrict__ out, int B, int C,
+                                                                         E* __restrict__ out, int B, int C,
                                                                          int N, long long P, int chunks, int passes,
                                                                          int cgroups, int c_per_group, long long obs) {
-  extern __shared__ __attribute__((aligned(16))) float s_row1[];
+  constexpr int L = 16 / sizeof(E);
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_row1[];
+  const E* s_row = reinterpret_cast<const E*>(s_row1);
   const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
   const int per_b = chunks * cgroups;
   const int b = x + 8 * (y / per_b);
@@ -484,47 +561,39 @@ __global__ __launch_bounds__(kDma1Threads) void group_points_dma1_kernel(const f
   if (b >= B || c_begin >= c_end) return;
   const int t = threadIdx.x;
   const int wave = pp::wave_id_uniform();
-  const long long p0 = (long long)chunk * (kDma1Threads * 4 * V) + t * 4;
-  unsigned ii[V][4];
+  const long long p0 = (long long)chunk * (kDma1Threads * L * V) + t * L;
+  int ii[V][L];
 #pragma unroll
-  for (int v = 0; v < V; ++v) {
-    const pp::i4 q = *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p0 + (long long)v * (kDma1Threads * 4));
-    ii[v][0] = q.x; ii[v][1] = q.y; ii[v][2] = q.z; ii[v][3] = q.w;
-  }
-  const int n4 = N >> 2;
-  const pp::f4* __restrict__ row0 = reinterpret_cast<const pp::f4*>(points + (size_t)b * C * N);
-  float* __restrict__ out_b = out + (size_t)b * obs;
+  for (int v = 0; v < V; ++v) load_indices(ii[v], idx + (size_t)b * P + p0 + (long long)v * (kDma1Threads * L));
+  const int n16 = N >> (L == 4 ? 2 : 3);  // 16-byte units of a row
+  const u4v* __restrict__ row0 = reinterpret_cast<const u4v*>(points + (size_t)b * C * N);
+  E* __restrict__ out_b = out + (size_t)b * obs;
   for (int c = c_begin; c < c_end; ++c) {
-    const pp::f4* __restrict__ row = row0 + (size_t)c * n4;
+    const u4v* __restrict__ row = row0 + (size_t)c * n16;
     for (int k = 0; k < passes; ++k) {
       const int e = k * kDma1Threads + t;
-      const int src = e < n4 ? e : n4 - 1;
-      float* dst = s_row1 + (size_t)(k * kDma1Threads + wave * 64) * 4;
+      const int src = e < n16 ? e : n16 - 1;  // surplus lanes re-load the last unit into the buffer's slack
+      unsigned char* dst = s_row1 + (size_t)(k * kDma1Threads + wave * 64) * 16;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(row + src),
                                        (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    float* __restrict__ o = out_b + (size_t)c * P;
+    E* __restrict__ o = out_b + (size_t)c * P;
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-      pp::f4 r;
-      r.x = s_row1[ii[v][0]];
-      r.y = s_row1[ii[v][1]];
-      r.z = s_row1[ii[v][2]];
-      r.w = s_row1[ii[v][3]];
-      __builtin_nontemporal_store(r, reinterpret_cast<pp::f4*>(o + p0 + (long long)v * (kDma1Threads * 4)));
-    }
+    for (int v = 0; v < V; ++v)
+      store16_nt(o + p0 + (long long)v * (kDma1Threads * L), gather16(s_row, ii[v]));
     __builtin_amdgcn_s_barrier();  // every wave has read the row: the next one may land
     asm volatile("" ::: "memory");
   }
 }
 
-template <int V>
-bool launch_group_dma1(const float* points, const int* idx, float* out, int B, int C, int N, long long P,
+template <typename E, int V>
+bool launch_group_dma1(const E* points, const int* idx, E* out, int B, int C, int N, long long P,
                        long long obs, hipStream_t s) {
-  const long long per_block = (long long)kDma1Threads * 4 * V;
+  constexpr int L = 16 / sizeof(E);
+  const long long per_block = (long long)kDma1Threads * L * V;
   if (P % per_block != 0) return false;
   const long long chunks = P / per_block;
   const long long base = 8LL * ((B + 7) / 8) * chunks;
@@ -532,13 +601,13 @@ bool launch_group_dma1(const float* points, const int* idx, float* out, int B, i
   while (base * cgroups < 512 && cgroups * 2 <= C) cgroups *= 2;
   const int c_per_group = (C + cgroups - 1) / cgroups;
   const long long blocks = base * cgroups;
-  const int n4 = N / 4;
-  const int passes = (n4 + kDma1Threads - 1) / kDma1Threads;
+  const int n16 = N / L;
+  const int passes = (n16 + kDma1Threads - 1) / kDma1Threads;
   const size_t lds = (size_t)passes * kDma1Threads * 16;
   if (lds > 72 * 1024 || chunks > 0x7fffffLL || blocks > 0x7fffffffLL) return false;
   static pp::DeviceFlags lds_ok;
-  if (pp::allow_big_lds(group_points_dma1_kernel<V>, 80 * 1024, lds_ok) != hipSuccess) return false;  // (another kernel)
-  group_points_dma1_kernel<V><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
+  if (pp::allow_big_lds(group_points_dma1_kernel<E, V>, 80 * 1024, lds_ok) != hipSuccess) return false;  // (another kernel)
+  group_points_dma1_kernel<E, V><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
       points, idx, out, B, C, N, P, (int)chunks, passes, cgroups, c_per_group, obs);
   return true;
 }
@@ -562,6 +631,58 @@ bool launch_group_lds(const float* points, const int* idx, float* out, int B, in
     group_points_lds_kernel<V, 4><<<grid, block, lds, s>>>(points, idx, out, B, C, N, P, (int)chunks, obs);
   else
     group_points_lds_kernel<V, 8><<<grid, block, lds, s>>>(points, idx, out, B, C, N, P, (int)chunks, obs);
+  return true;
+}
+
+// The 16-bit VGPR-staged form: a 512-thread workgroup owns 512 * 8 * V consecutive positions of one batch element,
+// keeps their indices in registers for all C channels and streams 16-byte stores; the last chunk may be ragged
+// (P % 8 == 0: an octet exists whole or not at all).  Unlike group_points_lds_kernel it loads each row between the
+// barriers with tracked loads: no prefetch of the next row, no vm_wait, no FULL split.
+// Requires the vector conditions, N % 8 == 0 and 16-byte aligned points; 2 N bytes of LDS.
+template <int V>
+__global__ __launch_bounds__(512) void group_points_lds_b16_kernel(const u16* __restrict__ points,
+                                                                   const int* __restrict__ idx,
+                                                                   u16* __restrict__ out, int B, int C, int N,
+                                                                   long long P, int chunks, long long obs) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_r16[];
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int b = x + 8 * (y / chunks);
+  const int chunk = y % chunks;
+  if (b >= B) return;
+  const int t = threadIdx.x;
+  const long long p0 = (long long)chunk * (512 * 8 * V) + t * 8;
+  pp::i4 ia[V], ic[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const long long p = p0 + (long long)v * 4096;
+    ia[v] = p < P ? *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p) : pp::i4{0, 0, 0, 0};
+    ic[v] = p < P ? *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p + 4) : pp::i4{0, 0, 0, 0};
+  }
+  const int n8 = N >> 3;
+  const u4v* __restrict__ rows = reinterpret_cast<const u4v*>(points + (size_t)b * C * N);
+  u16* __restrict__ out_b = out + (size_t)b * obs;
+  for (int c = 0; c < C; ++c) {
+    __syncthreads();  // everyone is done gathering from the previous row
+    for (int e = t; e < n8; e += 512) reinterpret_cast<u4v*>(s_r16)[e] = rows[(size_t)c * n8 + e];
+    __syncthreads();
+    u16* __restrict__ o = out_b + (size_t)c * P;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const long long p = p0 + (long long)v * 4096;
+      const u4v r = gather8(s_r16, ia[v], ic[v]);
+      if (p < P) *reinterpret_cast<u4v*>(o + p) = r;
+    }
+  }
+}
+
+bool launch_group_lds_b16(const u16* points, const int* idx, u16* out, int B, int C, int N, long long P,
+                          long long obs, hipStream_t s) {
+  constexpr int V = 4;  // the one instantiation
+  const long long chunks = (P + 512LL * 8 * V - 1) / (512LL * 8 * V);
+  const long long blocks = 8LL * ((B + 7) / 8) * chunks;
+  if (chunks > 0x7fffffLL || blocks > 0x7fffffffLL) return false;
+  group_points_lds_b16_kernel<V><<<dim3((unsigned)blocks), dim3(512), (size_t)N * 2, s>>>(points, idx, out, B, C, N, P,
+                                                                                        (int)chunks, obs);
   return true;
 }
 
@@ -989,16 +1110,94 @@ __global__ __launch_bounds__(1024) void three_interpolate_rows_kernel(const floa
   }
 }
 
-template <int CG, bool VEC>
-static int launch_three_interpolate_rows(const float* points, const int* idx, const float* weight, float* out,
+// The 16-bit channel-group form, the algorithm of three_interpolate_rows_kernel: CG rows of T staged in LDS (2 M bytes
+// each), widened as they are gathered; the canonical chain in fp32 and one rounding.  VEC: M % 8 == 0, N % 4 == 0,
+// points / idx / weight 16-byte and out 8-byte aligned -- 16-byte staging, four n per lane, one 8-byte store per channel.
+// A kernel of its own because no common source compiles to both kernels' instruction streams (NOTEBOOK.md, "one set of
+// forward kernels"); the two share launch_three_interpolate_rows.
+template <int CG, bool VEC, typename T>
+__global__ __launch_bounds__(1024) void three_interpolate_rows_b16_kernel(const T* __restrict__ points,
+                                                                          const int* __restrict__ idx,
+                                                                          const float* __restrict__ weight,
+                                                                          T* __restrict__ out, int B, int C,
+                                                                          int M, int N) {
+  extern __shared__ __attribute__((aligned(16))) u16 s_i16[];  // [CG][M] of T
+  T* s_rows = reinterpret_cast<T*>(s_i16);
+  const int groups = (C + CG - 1) / CG;
+  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
+  const int b = x + 8 * (y / groups);
+  if (b >= B) return;
+  const int c0 = (y % groups) * CG;
+  const int nc = min(CG, C - c0);
+  const int t = threadIdx.x;
+  for (int k = 0; k < nc; ++k) {
+    const T* __restrict__ rowp = points + ((size_t)b * C + c0 + k) * M;
+    if constexpr (VEC) {
+      for (int e = t; e < (M >> 3); e += 1024)
+        reinterpret_cast<u4v*>(s_rows + (size_t)k * M)[e] = reinterpret_cast<const u4v*>(rowp)[e];
+    } else {
+      for (int e = t; e < M; e += 1024) s_rows[(size_t)k * M + e] = rowp[e];
+    }
+  }
+  __syncthreads();
+  if constexpr (VEC) {
+    for (int n0 = 4 * t; n0 < N; n0 += 4096) {
+      int ii[12];
+      float ww[12];
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        const pp::i4 q = reinterpret_cast<const pp::i4*>(idx + ((size_t)b * N + n0) * 3)[e];
+        const pp::f4 w = reinterpret_cast<const pp::f4*>(weight + ((size_t)b * N + n0) * 3)[e];
+        ii[4 * e] = q.x; ii[4 * e + 1] = q.y; ii[4 * e + 2] = q.z; ii[4 * e + 3] = q.w;
+        ww[4 * e] = w.x; ww[4 * e + 1] = w.y; ww[4 * e + 2] = w.z; ww[4 * e + 3] = w.w;
+      }
+#pragma unroll
+      for (int k = 0; k < CG; ++k)
+        if (k < nc) {
+          const T* __restrict__ sr = s_rows + (size_t)k * M;
+          T r[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            r[j] = pp::narrow<T>(__builtin_fmaf(ww[3 * j + 2], pp::widen(sr[ii[3 * j + 2]]),
+                                                __builtin_fmaf(ww[3 * j], pp::widen(sr[ii[3 * j]]),
+                                                               ww[3 * j + 1] * pp::widen(sr[ii[3 * j + 1]]))));
+          u2v packed;
+          __builtin_memcpy(&packed, r, 8);
+          *reinterpret_cast<u2v*>(out + ((size_t)b * C + c0 + k) * N + n0) = packed;
+        }
+    }
+  } else {  // no alignment assumed: one n per lane and step, 2-byte stores
+    for (int n = t; n < N; n += 1024) {
+      const int* __restrict__ id = idx + ((size_t)b * N + n) * 3;
+      const float* __restrict__ w = weight + ((size_t)b * N + n) * 3;
+      const int i0 = id[0], i1 = id[1], i2 = id[2];
+      const float w0 = w[0], w1 = w[1], w2 = w[2];
+#pragma unroll
+      for (int k = 0; k < CG; ++k)
+        if (k < nc) {
+          const T* __restrict__ sr = s_rows + (size_t)k * M;
+          out[((size_t)b * C + c0 + k) * N + n] = pp::narrow<T>(
+              __builtin_fmaf(w2, pp::widen(sr[i2]), __builtin_fmaf(w0, pp::widen(sr[i0]), w1 * pp::widen(sr[i1]))));
+        }
+    }
+  }
+}
+
+// one launcher for both: the fp32 kernel for float, the widening one for pp::f16 / pp::bf16
+template <int CG, bool VEC, typename T>
+static int launch_three_interpolate_rows(const T* points, const int* idx, const float* weight, T* out,
                                          int B, int C, int M, int N, hipStream_t s) {
+  void (*kernel)(const T*, const int*, const float*, T*, int, int, int, int);
+  if constexpr (std::is_same<T, float>::value)
+    kernel = three_interpolate_rows_kernel<CG, VEC>;
+  else
+    kernel = three_interpolate_rows_b16_kernel<CG, VEC, T>;
   static pp::DeviceFlags ok;
-  const hipError_t e = pp::allow_big_lds(three_interpolate_rows_kernel<CG, VEC>, 152 * 1024, ok);
+  const hipError_t e = pp::allow_big_lds(kernel, 152 * 1024, ok);
   if (e != hipSuccess) return (int)e;
   const long long wgs = 8LL * ((B + 7) / 8) * ((C + CG - 1) / CG);
   if (wgs > 0x7fffffffLL) return PP_EINVAL;
-  three_interpolate_rows_kernel<CG, VEC><<<dim3((unsigned)wgs), dim3(1024), (size_t)CG * M * sizeof(float), s>>>(
-      points, idx, weight, out, B, C, M, N);
+  kernel<<<dim3((unsigned)wgs), dim3(1024), (size_t)CG * M * sizeof(T), s>>>(points, idx, weight, out, B, C, M, N);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
 }
@@ -1104,56 +1303,77 @@ bool grid_ok(long long x, long long y, long long z) {
 
 }  // namespace
 
-// 0 = automatic; 1 = force the global-gather kernel (tests and tuning)
+// ================================================================================================
+// The forward dispatches: one per operator, a template on the element (float; u16 for the copies of fp16 / bf16
+// features; pp::f16 / pp::bf16 where there is arithmetic), written in L = 16 / sizeof(E) elements per 16 bytes.  Where
+// the two element sizes follow different policies, the difference stands once, under `if constexpr`.
+// ================================================================================================
+// 0 = automatic; 1 = force the global-gather kernel; 2 = 16-bit: the LDS form wherever the row fits, fp32: as 0
+// (tests and tuning)
 static pp::Knob g_gather_variant;
 extern "C" void pp_debug_set_gather_variant(int v) { g_gather_variant.set(v); }
 
-extern "C" int pp_gather_forward_f32(const float* points, const int* idx, float* out, int B, int C,
-                                     int N, int M, void* stream) {
+namespace {
+
+template <typename E>
+int gather_forward(const E* points, const int* idx, E* out, int B, int C, int N, int M, void* stream) {
+  constexpr int L = 16 / sizeof(E);
+  constexpr bool k32 = sizeof(E) == 4;
   if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
   if (B == 0 || C == 0 || M == 0) return PP_OK;
   if (!points || !idx || !out || N == 0) return PP_EINVAL;
-  // LDS-staged rows: the row fits, reading whole rows pays (N <= 16 M); 16-byte variant when rows and
-  // index quads are aligned, 4-byte variant otherwise
-  if (g_gather_variant != 1 && (size_t)N * sizeof(float) <= 152 * 1024 && (long long)N <= 16LL * M &&
-      (long long)B * C >= 512 && M >= 1024) {
-    const bool vec = N % 4 == 0 && M % 4 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
-                     (uintptr_t)out % 16 == 0 && N <= 16384;
+  hipStream_t s = (hipStream_t)stream;
+  const int gv = g_gather_variant;
+  // LDS-staged rows: the row fits, reading whole rows pays (N <= 16 M); the 16-byte variant when rows and the lanes'
+  // index runs are aligned, the element-sized variant otherwise
+  bool pays = (long long)N <= 16LL * M && (long long)B * C >= 512 && M >= 1024;
+  if constexpr (!k32) pays = pays || gv == 2;  // 16-bit: knob 2 takes the form wherever the row fits (fp32 reads 2 as 0)
+  if (gv != 1 && (size_t)N * sizeof(E) <= 152 * 1024 && pays) {
+    bool vec = N % L == 0 && M % L == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
+               (uintptr_t)out % 16 == 0;
+    if constexpr (k32) vec = vec && N <= 16384;  // fp32: the vector kernel prefetches a row of at most 64 KiB
     int cpb = 4;
     while (cpb > 1 && 8LL * ((B + 7) / 8) * ((C + cpb - 1) / cpb) < 1024) cpb /= 2;
     const int groups = (C + cpb - 1) / cpb;
     const long long wgs = 8LL * ((B + 7) / 8) * groups;
     if (wgs <= 0x7fffffffLL) {
-      const dim3 grid((unsigned)wgs), block(1024);
-      const size_t lds = (size_t)N * sizeof(float);
-      hipStream_t s = (hipStream_t)stream;
-      const int n4 = N / 4;
       static pp::DeviceFlags ok1, ok2, ok4, oks;
-      if (!vec) {
-        if (pp::allow_big_lds(gather_fwd_lds_kernel<1, false>, 152 * 1024, oks) != hipSuccess) return PP_EINVAL;
-        gather_fwd_lds_kernel<1, false><<<grid, block, lds, s>>>(points, idx, out, B, C, N, M, cpb, groups);
-      } else if (n4 <= 1024) {
-        if (pp::allow_big_lds(gather_fwd_lds_kernel<1, true>, 64 * 1024, ok1) != hipSuccess) return PP_EINVAL;
-        gather_fwd_lds_kernel<1, true><<<grid, block, lds, s>>>(points, idx, out, B, C, N, M, cpb, groups);
-      } else if (n4 <= 2048) {
-        if (pp::allow_big_lds(gather_fwd_lds_kernel<2, true>, 64 * 1024, ok2) != hipSuccess) return PP_EINVAL;
-        gather_fwd_lds_kernel<2, true><<<grid, block, lds, s>>>(points, idx, out, B, C, N, M, cpb, groups);
-      } else {
-        if (pp::allow_big_lds(gather_fwd_lds_kernel<4, true>, 64 * 1024, ok4) != hipSuccess) return PP_EINVAL;
-        gather_fwd_lds_kernel<4, true><<<grid, block, lds, s>>>(points, idx, out, B, C, N, M, cpb, groups);
+      auto launch = [&](auto kernel, int lds_limit, pp::DeviceFlags& ok) -> int {
+        if (pp::allow_big_lds(kernel, lds_limit, ok) != hipSuccess) return PP_EINVAL;
+        kernel<<<dim3((unsigned)wgs), dim3(1024), (size_t)N * sizeof(E), s>>>(points, idx, out, B, C, N, M, cpb, groups);
+        PP_RETURN_IF_LAUNCH_FAILED();
+        return PP_OK;
+      };
+      if (!vec) return launch(gather_fwd_lds_kernel<1, false, E>, 152 * 1024, oks);
+      if constexpr (k32) {  // fp32: KR = 16-byte units per thread of the prefetched row; LDS limit 64 KiB
+        const int n4 = N / 4;
+        if (n4 <= 1024) return launch(gather_fwd_lds_kernel<1, true>, 64 * 1024, ok1);
+        if (n4 <= 2048) return launch(gather_fwd_lds_kernel<2, true>, 64 * 1024, ok2);
+        return launch(gather_fwd_lds_kernel<4, true>, 64 * 1024, ok4);
+      } else {  // 16-bit: one vector kernel, any row that fits
+        return launch(gather_fwd_lds_b16_kernel, 152 * 1024, ok1);
       }
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
     }
   }
   const long long cols = (M + 255) / 256;
   const int cpb = pick_c_per_block(cols, B, C);
   const long long gy = (C + cpb - 1) / cpb;
   if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  gather_fwd_kernel<float><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                             (hipStream_t)stream>>>(points, idx, out, C, N, M, cpb);
+  gather_fwd_kernel<E><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0, s>>>(points, idx, out, C, N, M,
+                                                                                           cpb);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_gather_forward_f32(const float* points, const int* idx, float* out, int B, int C,
+                                     int N, int M, void* stream) {
+  return gather_forward(points, idx, out, B, C, N, M, stream);
+}
+extern "C" int pp_gather_forward_b16(const void* points, const int* idx, void* out, int B, int C, int N, int M,
+                                     void* stream) {
+  return gather_forward((const u16*)points, idx, (u16*)out, B, C, N, M, stream);
 }
 
 // 0 = automatic; 1 = force the one-wave-per-64-centres kernel (tests and tuning)
@@ -1212,21 +1432,20 @@ int ball_query_scan_unusable(const float* new_xyz, const float* xyz, int* idx, i
 }
 }  // namespace pp
 
-// 0 = automatic; 1 = force the global-gather kernel; 2/4/8 = force the VGPR-staged LDS kernel with that many index
-// quads per thread; 604/608/616 = the LDS-DMA kernel with 4/8/16 quads where the positions fill whole chunks, the
-// VGPR-staged one elsewhere; any other value above 100 = no LDS-DMA kernel (tests and tuning)
+// 0 = automatic; 1 = force the global-gather kernel; 2/4/8 = force the VGPR-staged LDS kernel (fp32: with that many
+// index quads per thread; 16-bit: its one instantiation); 604/608/616 = the LDS-DMA kernel on chunks of 8192 / 16384 /
+// 32768 positions where the positions fill whole chunks, the VGPR-staged one elsewhere; any other value above 100 = no
+// LDS-DMA kernel (tests and tuning)
 static pp::Knob g_group_variant;
 extern "C" void pp_debug_set_group_points_variant(int v) { g_group_variant.set(v); }
 
-extern "C" int pp_group_points_f32(const float* points, const int* idx, float* out, int B, int C,
-                                   int N, int npoint, int nsample, void* stream) {
-  return pp_group_points_strided_f32(points, idx, out, B, C, N, npoint, nsample,
-                                     (long long)C * npoint * nsample, stream);
-}
+namespace {
 
-extern "C" int pp_group_points_strided_f32(const float* points, const int* idx, float* out, int B, int C,
-                                           int N, int npoint, int nsample, long long out_batch_stride,
-                                           void* stream) {
+template <typename E>
+int group_points_strided(const E* points, const int* idx, E* out, int B, int C, int N, int npoint, int nsample,
+                         long long out_batch_stride, void* stream) {
+  constexpr int L = 16 / sizeof(E);
+  constexpr bool k32 = sizeof(E) == 4;
   if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
   const long long P = (long long)npoint * nsample;
   const long long obs = out_batch_stride;
@@ -1234,67 +1453,91 @@ extern "C" int pp_group_points_strided_f32(const float* points, const int* idx, 
   if (B == 0 || C == 0 || P == 0) return PP_OK;
   if (!points || !idx || !out || N == 0) return PP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const bool vec4 = (P % 4 == 0) && (obs % 4 == 0) && ((uintptr_t)idx % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  // LDS-staged form: row fits 64 KiB (two workgroups per CU), rows 16-byte aligned, enough channels
-  // to amortise keeping the indices in registers, enough positions to fill the chip
-  if (g_group_variant != 1 && vec4 && N % 4 == 0 && (uintptr_t)points % 16 == 0 &&
-      (size_t)N * sizeof(float) <= 64 * 1024 && C >= 4 && (long long)B * P >= 256LL * 2048) {
-    const long long per_cu = (long long)B * P / 512;  // positions per half-CU
+  const int gv = g_group_variant;
+  const bool vec = (P % L == 0) && (obs % L == 0) && ((uintptr_t)idx % 16 == 0) && ((uintptr_t)out % 16 == 0);
+  bool fills = (long long)B * P >= 256LL * 2048;  // enough positions to fill the chip
+  // 16-bit: a knob value that names an LDS form takes it below that size too (tests); fp32: the floor always holds
+  if constexpr (!k32) fills = fills || gv != 0;
+  // LDS-staged forms: row within 64 KiB (two workgroups per CU), rows 16-byte aligned, enough channels to amortise
+  // keeping the indices in registers
+  if (gv != 1 && vec && N % L == 0 && (uintptr_t)points % 16 == 0 && (size_t)N * sizeof(E) <= 64 * 1024 && C >= 4 &&
+      fills) {
+    // the LDS-DMA form wherever the positions fill whole chunks of 32768, 16384 or 8192 (16 / 8 / 4 index quads per
+    // thread, or 8 / 4 / 2 octets): measured round 6 at or ahead of every other form on every shape it can take
+    // (tools/group_shapes_time.py); the output is written with non-temporal stores (4 GiB at config 4, nothing of it is
+    // read back from the caches)
     bool ok = false;
-    // the LDS-DMA form wherever the positions fill whole chunks (16, 8 or 4 index quads per thread): measured round 6
-    // at or ahead of every other form on every shape it can take (tools/group_shapes_time.py); the output is written
-    // with non-temporal stores (4 GiB at config 4, nothing of it is read back from the caches)
-    const int gv = g_group_variant;
-    if (gv == 616 || gv == 0) ok = launch_group_dma1<16>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 608 || gv == 0)) ok = launch_group_dma1<8>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 604 || gv == 0)) ok = launch_group_dma1<4>(points, idx, out, B, C, N, P, obs, s);
-    if (ok) {
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
+    if (gv == 616 || gv == 0) ok = launch_group_dma1<E, 64 / L>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok && (gv == 608 || gv == 0)) ok = launch_group_dma1<E, 32 / L>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok && (gv == 604 || gv == 0)) ok = launch_group_dma1<E, 16 / L>(points, idx, out, B, C, N, P, obs, s);
+    if (!ok) {  // ragged chunks, or forced by 2 / 4 / 8 / a value above 100: the VGPR-staged form
+      if constexpr (k32) {
+        // 8 / 4 / 2 index quads per thread by the positions a CU gets (> 100: the values 604 / 608 / 616 on shapes
+        // their LDS-DMA kernel cannot take)
+        const long long per_cu = (long long)B * P / 512;  // positions per half-CU
+        if (gv == 8 || ((gv == 0 || gv > 100) && per_cu >= 512LL * 4 * 8))
+          ok = launch_group_lds<8>(points, idx, out, B, C, N, P, obs, s);
+        else if (gv == 4 || (gv == 0 && per_cu >= 512LL * 4 * 4))
+          ok = launch_group_lds<4>(points, idx, out, B, C, N, P, obs, s);
+        else
+          ok = launch_group_lds<2>(points, idx, out, B, C, N, P, obs, s);
+      } else {
+        ok = launch_group_lds_b16(points, idx, out, B, C, N, P, obs, s);
+      }
     }
-    // ragged chunks: the VGPR-staged form, 8 / 4 / 2 index quads per thread by the positions a CU gets (> 100: the
-    // values 604 / 608 / 616 on shapes their LDS-DMA kernel cannot take)
-    if (g_group_variant == 8 || ((g_group_variant == 0 || g_group_variant > 100) && per_cu >= 512LL * 4 * 8))
-      ok = launch_group_lds<8>(points, idx, out, B, C, N, P, obs, s);
-    else if (g_group_variant == 4 || (g_group_variant == 0 && per_cu >= 512LL * 4 * 4))
-      ok = launch_group_lds<4>(points, idx, out, B, C, N, P, obs, s);
-    else
-      ok = launch_group_lds<2>(points, idx, out, B, C, N, P, obs, s);
     if (ok) {
       PP_RETURN_IF_LAUNCH_FAILED();
       return PP_OK;
     }
   }
-  // unaligned shapes, or rows beyond 64 KiB: the 4-byte LDS-staged form -- from 2^28 output elements (measured round 6:
-  // 1.89 against 7.7 ms for the global gather at config 4 less one point and one sample, but 0.27 against 0.21 at a
-  // fifth of a GiB and 0.079 against 0.050 at 69 MB: tools/group_shapes_time.py)
-  if (g_group_variant != 1 && (size_t)N * sizeof(float) <= 152 * 1024 && C >= 4 &&
-      (long long)B * P >= 256LL * 2048 && (g_group_variant != 0 || (long long)B * P * C >= (1LL << 28))) {
-    constexpr int V = 16;
-    const long long chunks = (P + 1024LL * V - 1) / (1024LL * V);
-    const long long blocks = 8LL * ((B + 7) / 8) * chunks;
-    if (chunks <= 0x7fffffLL && blocks <= 0x7fffffffLL) {
-      static pp::DeviceFlags ok_s;
-      const hipError_t e = pp::allow_big_lds(group_points_lds_scalar_kernel<V>, 152 * 1024, ok_s);
-      if (e != hipSuccess) return (int)e;
-      group_points_lds_scalar_kernel<V><<<dim3((unsigned)blocks), dim3(1024), (size_t)N * sizeof(float), s>>>(
-          points, idx, out, B, C, N, P, (int)chunks, obs);
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
+  // fp32 only -- unaligned shapes, or rows beyond 64 KiB: the 4-byte LDS-staged form, from 2^28 output elements (measured
+  // round 6: 1.89 against 7.7 ms for the global gather at config 4 less one point and one sample, but 0.27 against 0.21
+  // at a fifth of a GiB and 0.079 against 0.050 at 69 MB: tools/group_shapes_time.py).  No 16-bit form of it.
+  if constexpr (k32) {
+    if (gv != 1 && (size_t)N * sizeof(float) <= 152 * 1024 && C >= 4 && (long long)B * P >= 256LL * 2048 &&
+        (gv != 0 || (long long)B * P * C >= (1LL << 28))) {
+      constexpr int V = 16;
+      const long long chunks = (P + 1024LL * V - 1) / (1024LL * V);
+      const long long blocks = 8LL * ((B + 7) / 8) * chunks;
+      if (chunks <= 0x7fffffLL && blocks <= 0x7fffffffLL) {
+        static pp::DeviceFlags ok_s;
+        const hipError_t e = pp::allow_big_lds(group_points_lds_scalar_kernel<V>, 152 * 1024, ok_s);
+        if (e != hipSuccess) return (int)e;
+        group_points_lds_scalar_kernel<V><<<dim3((unsigned)blocks), dim3(1024), (size_t)N * sizeof(float), s>>>(
+            points, idx, out, B, C, N, P, (int)chunks, obs);
+        PP_RETURN_IF_LAUNCH_FAILED();
+        return PP_OK;
+      }
     }
   }
-  const long long threads = vec4 ? P / 4 : P;
+  const long long threads = vec ? P / L : P;
   const long long cols = (threads + 255) / 256;
   const int cpb = pick_c_per_block(cols, B, C);
   const long long gy = (C + cpb - 1) / cpb;
   if (!grid_ok(cols, gy, B)) return PP_EINVAL;
   const dim3 grid((unsigned)cols, (unsigned)gy, (unsigned)B);
-  if (vec4)
-    group_points_kernel<true><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
+  if (vec)
+    group_points_kernel<E, true><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
   else
-    group_points_kernel<false><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
+    group_points_kernel<E, false><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_group_points_f32(const float* points, const int* idx, float* out, int B, int C,
+                                   int N, int npoint, int nsample, void* stream) {
+  return group_points_strided(points, idx, out, B, C, N, npoint, nsample, (long long)C * npoint * nsample, stream);
+}
+extern "C" int pp_group_points_strided_f32(const float* points, const int* idx, float* out, int B, int C,
+                                           int N, int npoint, int nsample, long long out_batch_stride,
+                                           void* stream) {
+  return group_points_strided(points, idx, out, B, C, N, npoint, nsample, out_batch_stride, stream);
+}
+extern "C" int pp_group_points_strided_b16(const void* points, const int* idx, void* out, int B, int C, int N,
+                                           int npoint, int nsample, long long out_batch_stride, void* stream) {
+  return group_points_strided((const u16*)points, idx, (u16*)out, B, C, N, npoint, nsample, out_batch_stride, stream);
 }
 
 static int three_nn_launch(const float* unknown, const float* known, float* dist2, int* idx, int B, int N,
@@ -1316,53 +1559,85 @@ extern "C" int pp_three_nn_f32(const float* unknown, const float* known, float* 
   return three_nn_launch(unknown, known, dist2, idx, B, N, M, nullptr, stream);
 }
 
-// 0 = automatic; 1 = force the global-gather kernel; 2 = no channel-group form (row-at-a-time LDS
-// form where it applies)   (tests and tuning)
+// 0 = automatic; 1 = force the global-gather kernel; 2 = no channel-group form (fp32: the row-at-a-time LDS form
+// where it applies; 16-bit: the global form); 3 = 16-bit: the channel-group form wherever the rows fit, fp32: as 0
+// (tests and tuning)
 static pp::Knob g_interp_variant;
 extern "C" void pp_debug_set_three_interpolate_variant(int v) { g_interp_variant.set(v); }
 
-extern "C" int pp_three_interpolate_f32(const float* points, const int* idx, const float* weight,
-                                        float* out, int B, int C, int M, int N, void* stream) {
+namespace {
+
+template <typename T>
+int three_interpolate(const T* points, const int* idx, const float* weight, T* out, int B, int C, int M, int N,
+                      void* stream) {
+  constexpr int L = 16 / sizeof(T);
+  constexpr bool k32 = sizeof(T) == 4;
   if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
   if (B == 0 || C == 0 || N == 0) return PP_OK;
   if (!points || !idx || !weight || !out || M == 0) return PP_EINVAL;
-  // channel-group form (rows staged once, §three_interpolate_rows_kernel): as many whole rows per
-  // workgroup as keep two workgroups on a CU (4 x 16 KiB at M = 4096), fewer for long rows; the 16-byte
-  // variant when everything is aligned, the 4-byte variant otherwise
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = M % 4 == 0 && N % 4 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
-                   (uintptr_t)weight % 16 == 0 && (uintptr_t)out % 16 == 0;
-  const size_t rowb = (size_t)M * sizeof(float);
-  if (g_interp_variant != 1 && g_interp_variant != 2 && rowb <= 152 * 1024 && N >= 2048 &&
-      8LL * ((B + 7) / 8) * ((C + 3) / 4) >= 256) {
-    const int cg = (4 * rowb <= 64 * 1024 && C >= 4) ? 4 : ((2 * rowb <= 152 * 1024 && C >= 2) ? 2 : 1);
+  const int iv = g_interp_variant;
+  // the 16-byte variants: aligned rows, index and weight quads; out aligned to a lane's four elements (fp32: 16 bytes,
+  // 16-bit: 8)
+  const bool vec = M % L == 0 && N % 4 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
+                   (uintptr_t)weight % 16 == 0 && (uintptr_t)out % (4 * sizeof(T)) == 0;
+  // channel-group form (rows staged once, §three_interpolate_rows_kernel): as many whole rows per workgroup as keep two
+  // workgroups on a CU (4 x 16 KiB at M = 4096 floats), fewer for long rows
+  const size_t rowb = (size_t)M * sizeof(T);
+  bool enough = N >= 2048 && 8LL * ((B + 7) / 8) * ((C + 3) / 4) >= 256;
+  if constexpr (!k32) enough = enough || iv == 3;  // 16-bit: knob 3 waives both floors (tests)
+  if (iv != 1 && iv != 2 && rowb <= 152 * 1024 && enough) {
+    int cg = (4 * rowb <= 64 * 1024 && C >= 4) ? 4 : 1;
+    if constexpr (k32) {  // fp32 only: two rows where four do not fit
+      if (cg == 1 && 2 * rowb <= 152 * 1024 && C >= 2) cg = 2;
+    }
     if (vec) {
       if (cg == 4) return launch_three_interpolate_rows<4, true>(points, idx, weight, out, B, C, M, N, s);
-      if (cg == 2) return launch_three_interpolate_rows<2, true>(points, idx, weight, out, B, C, M, N, s);
+      if constexpr (k32)
+        if (cg == 2) return launch_three_interpolate_rows<2, true>(points, idx, weight, out, B, C, M, N, s);
       return launch_three_interpolate_rows<1, true>(points, idx, weight, out, B, C, M, N, s);
     }
     if (cg == 4) return launch_three_interpolate_rows<4, false>(points, idx, weight, out, B, C, M, N, s);
-    if (cg == 2) return launch_three_interpolate_rows<2, false>(points, idx, weight, out, B, C, M, N, s);
+    if constexpr (k32)
+      if (cg == 2) return launch_three_interpolate_rows<2, false>(points, idx, weight, out, B, C, M, N, s);
     return launch_three_interpolate_rows<1, false>(points, idx, weight, out, B, C, M, N, s);
   }
-  // row-at-a-time LDS form: 16-byte aligned rows and quads, row within 64 KiB, enough channels to amortise
-  if (g_interp_variant != 1 && vec && M <= 16384 && C >= 4 && (long long)B * N >= 64 * 2048) {
-    const int m4 = M / 4;
-    if (m4 <= 512) launch_three_interpolate_lds<1>(points, idx, weight, out, B, C, M, N, s);
-    else if (m4 <= 1024) launch_three_interpolate_lds<2>(points, idx, weight, out, B, C, M, N, s);
-    else if (m4 <= 2048) launch_three_interpolate_lds<4>(points, idx, weight, out, B, C, M, N, s);
-    else launch_three_interpolate_lds<8>(points, idx, weight, out, B, C, M, N, s);
-    PP_RETURN_IF_LAUNCH_FAILED();
-    return PP_OK;
+  // fp32 only, and what its knob value 2 selects -- the row-at-a-time LDS form: 16-byte aligned rows and quads, row
+  // within 64 KiB, enough channels to amortise
+  if constexpr (k32) {
+    if (iv != 1 && vec && M <= 16384 && C >= 4 && (long long)B * N >= 64 * 2048) {
+      const int m4 = M / 4;
+      if (m4 <= 512) launch_three_interpolate_lds<1>(points, idx, weight, out, B, C, M, N, s);
+      else if (m4 <= 1024) launch_three_interpolate_lds<2>(points, idx, weight, out, B, C, M, N, s);
+      else if (m4 <= 2048) launch_three_interpolate_lds<4>(points, idx, weight, out, B, C, M, N, s);
+      else launch_three_interpolate_lds<8>(points, idx, weight, out, B, C, M, N, s);
+      PP_RETURN_IF_LAUNCH_FAILED();
+      return PP_OK;
+    }
   }
   const long long cols = (N + 255) / 256;
   const int cpb = pick_c_per_block(cols, B, C);
   const long long gy = (C + cpb - 1) / cpb;
   if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  three_interpolate_kernel<float><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0,
-                                    (hipStream_t)stream>>>(points, idx, weight, out, C, M, N, cpb);
+  three_interpolate_kernel<T><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0, s>>>(
+      points, idx, weight, out, C, M, N, cpb);
   PP_RETURN_IF_LAUNCH_FAILED();
   return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_three_interpolate_f32(const float* points, const int* idx, const float* weight,
+                                        float* out, int B, int C, int M, int N, void* stream) {
+  return three_interpolate(points, idx, weight, out, B, C, M, N, stream);
+}
+extern "C" int pp_three_interpolate_f16(const void* points, const int* idx, const float* weight, void* out, int B,
+                                        int C, int M, int N, void* stream) {
+  return three_interpolate((const pp::f16*)points, idx, weight, (pp::f16*)out, B, C, M, N, stream);
+}
+extern "C" int pp_three_interpolate_bf16(const void* points, const int* idx, const float* weight, void* out, int B,
+                                         int C, int M, int N, void* stream) {
+  return three_interpolate((const pp::bf16*)points, idx, weight, (pp::bf16*)out, B, C, M, N, stream);
 }
 
 // ================================================================================================
@@ -1668,424 +1943,3 @@ extern "C" int pp_three_interpolate_grad_ordered_f32(const float* grad_out, cons
 PP_SCATTER_B16(f16, pp::f16)
 PP_SCATTER_B16(bf16, pp::bf16)
 #undef PP_SCATTER_B16
-
-// ================================================================================================
-// 16-bit features (DESIGN.md §4 "16-bit features"): gather_points, group_points and three_interpolate on fp16 / bf16
-// FEATURE tensors; indices stay int32, weights fp32.  Copies move 2-byte words (one set of kernels for both types);
-// arithmetic widens to fp32, runs the fp32 kernels' chain and rounds once; the backwards sum in the accumulators of
-// the fp32 forms (group_points_grad_lds64_kernel, three_interpolate_grad_lds64_kernel and ssa_apply_kernel are
-// templates on the element type) and WRITE grad_points.  No 16-bit floating-point atomics anywhere: a backward
-// without an atomic-free form for its shape returns PP_ENOTSUP.
-// The vector forms own EIGHT consecutive elements per lane (16 bytes); every guard names its real requirement, and the
-// 2-byte scalar forms serve any shape: a row (b,c) starts at byte (b*C+c)*N*2, aligned to 16 only if N % 8 == 0.
-// ================================================================================================
-namespace {
-
-typedef uint16_t u16;
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pack2(u16 lo, u16 hi) { return (unsigned)lo | ((unsigned)hi << 16); }
-__device__ __forceinline__ u4v gather8(const u16* s, const pp::i4& a, const pp::i4& b) {
-  return u4v{pack2(s[a.x], s[a.y]), pack2(s[a.z], s[a.w]), pack2(s[b.x], s[b.y]), pack2(s[b.z], s[b.w])};
-}
-
-// gather_points through the LDS (see gather_fwd_lds_kernel): the row is 2 N bytes; VEC: N % 8 == 0, M % 8 == 0 and
-// 16-byte aligned pointers -- 16-byte row loads, two index quads and one 16-byte store per lane
-template <bool VEC>
-__global__ __launch_bounds__(1024) void gather_fwd_lds_b16_kernel(const u16* __restrict__ points,
-                                                                  const int* __restrict__ idx,
-                                                                  u16* __restrict__ out, int B, int C, int N,
-                                                                  int M, int cpb, int groups) {
-  extern __shared__ __attribute__((aligned(16))) u16 s_g16[];
-  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
-  const int b = x + 8 * (y / groups);
-  if (b >= B) return;
-  const int c0 = (y % groups) * cpb;
-  const int c1 = min(C, c0 + cpb);
-  const int t = threadIdx.x;
-  const int* __restrict__ ib = idx + (size_t)b * M;
-  for (int c = c0; c < c1; ++c) {
-    __syncthreads();  // the previous row has been gathered
-    const u16* __restrict__ row = points + ((size_t)b * C + c) * N;
-    u16* __restrict__ o = out + ((size_t)b * C + c) * M;
-    if constexpr (VEC) {
-      for (int e = t; e < (N >> 3); e += 1024) reinterpret_cast<u4v*>(s_g16)[e] = reinterpret_cast<const u4v*>(row)[e];
-      __syncthreads();
-      for (int m = t * 8; m < M; m += 8192) {
-        const pp::i4 ia = *reinterpret_cast<const pp::i4*>(ib + m);
-        const pp::i4 ic = *reinterpret_cast<const pp::i4*>(ib + m + 4);
-        *reinterpret_cast<u4v*>(o + m) = gather8(s_g16, ia, ic);
-      }
-    } else {
-      for (int e = t; e < N; e += 1024) s_g16[e] = row[e];
-      __syncthreads();
-      for (int m = t; m < M; m += 1024) o[m] = s_g16[ib[m]];
-    }
-  }
-}
-
-// group_points, global gathers: VEC8 = a lane owns 8 consecutive (j,k) positions (P % 8 == 0, obs % 8 == 0, idx and
-// out 16-byte aligned; the rows need no alignment: they are read 2 bytes at a time); otherwise one position per lane
-template <bool VEC8>
-__global__ __launch_bounds__(256) void group_points_b16_kernel(const u16* __restrict__ points,
-                                                               const int* __restrict__ idx,
-                                                               u16* __restrict__ out, int C, int N,
-                                                               long long P, int c_per_block, long long obs) {
-  const int b = blockIdx.z;
-  const int c0 = blockIdx.y * c_per_block;
-  const int c1 = min(C, c0 + c_per_block);
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (VEC8) {
-    const long long p = t * 8;
-    if (p >= P) return;
-    const pp::i4 ia = *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p);
-    const pp::i4 ic = *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p + 4);
-    for (int c = c0; c < c1; ++c)
-      *reinterpret_cast<u4v*>(out + (size_t)b * obs + (size_t)c * P + p) =
-          gather8(points + ((size_t)b * C + c) * N, ia, ic);
-  } else {
-    if (t >= P) return;
-    const int i = idx[(size_t)b * P + t];
-    for (int c = c0; c < c1; ++c)
-      out[(size_t)b * obs + (size_t)c * P + t] = points[((size_t)b * C + c) * N + i];
-  }
-}
-
-// group_points, row staged in LDS through registers (see group_points_lds_kernel): a 512-thread workgroup owns
-// 512 * 8 * V consecutive positions of one batch element, keeps their indices in registers for all C channels and
-// streams 16-byte stores; the last chunk may be ragged (P % 8 == 0: an octet exists whole or not at all).
-// Requires the VEC8 conditions, N % 8 == 0 and 16-byte aligned points; 2 N bytes of LDS.
-template <int V>
-__global__ __launch_bounds__(512) void group_points_lds_b16_kernel(const u16* __restrict__ points,
-                                                                   const int* __restrict__ idx,
-                                                                   u16* __restrict__ out, int B, int C, int N,
-                                                                   long long P, int chunks, long long obs) {
-  extern __shared__ __attribute__((aligned(16))) u16 s_r16[];
-  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
-  const int b = x + 8 * (y / chunks);
-  const int chunk = y % chunks;
-  if (b >= B) return;
-  const int t = threadIdx.x;
-  const long long p0 = (long long)chunk * (512 * 8 * V) + t * 8;
-  pp::i4 ia[V], ic[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    const long long p = p0 + (long long)v * 4096;
-    ia[v] = p < P ? *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p) : pp::i4{0, 0, 0, 0};
-    ic[v] = p < P ? *reinterpret_cast<const pp::i4*>(idx + (size_t)b * P + p + 4) : pp::i4{0, 0, 0, 0};
-  }
-  const int n8 = N >> 3;
-  const u4v* __restrict__ rows = reinterpret_cast<const u4v*>(points + (size_t)b * C * N);
-  u16* __restrict__ out_b = out + (size_t)b * obs;
-  for (int c = 0; c < C; ++c) {
-    __syncthreads();  // everyone is done gathering from the previous row
-    for (int e = t; e < n8; e += 512) reinterpret_cast<u4v*>(s_r16)[e] = rows[(size_t)c * n8 + e];
-    __syncthreads();
-    u16* __restrict__ o = out_b + (size_t)c * P;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const long long p = p0 + (long long)v * 4096;
-      const u4v r = gather8(s_r16, ia[v], ic[v]);
-      if (p < P) *reinterpret_cast<u4v*>(o + p) = r;
-    }
-  }
-}
-
-// group_points, rows by LDS-DMA (see group_points_dma1_kernel): one wave instruction moves 1 KiB = 512 elements;
-// whole chunks of 512 * 8 * V positions only; non-temporal 16-byte stores
-template <int V>
-__global__ __launch_bounds__(kDma1Threads) void group_points_dma1_b16_kernel(const u16* __restrict__ points,
-                                                                             const int* __restrict__ idx,
-                                                                             u16* __restrict__ out, int B, int C, int N,
-                                                                             long long P, int chunks, int passes,
-                                                                             int cgroups, int c_per_group,
-                                                                             long long obs) {
-  extern __shared__ __attribute__((aligned(16))) u16 s_d16[];
-  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
-  const int per_b = chunks * cgroups;
-  const int b = x + 8 * (y / per_b);
-  const int rem = y % per_b;
-  const int chunk = rem / cgroups;
-  const int c_begin = (rem % cgroups) * c_per_group;
-  const int c_end = min(C, c_begin + c_per_group);
-  if (b >= B || c_begin >= c_end) return;
-  const int t = threadIdx.x;
-  const int wave = pp::wave_id_uniform();
-  const long long p0 = (long long)chunk * (kDma1Threads * 8 * V) + t * 8;
-  pp::i4 ia[V], ic[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    const int* q = idx + (size_t)b * P + p0 + (long long)v * (kDma1Threads * 8);
-    ia[v] = *reinterpret_cast<const pp::i4*>(q);
-    ic[v] = *reinterpret_cast<const pp::i4*>(q + 4);
-  }
-  const int n8 = N >> 3;  // 16-byte units of a row
-  const u4v* __restrict__ row0 = reinterpret_cast<const u4v*>(points + (size_t)b * C * N);
-  u16* __restrict__ out_b = out + (size_t)b * obs;
-  for (int c = c_begin; c < c_end; ++c) {
-    const u4v* __restrict__ row = row0 + (size_t)c * n8;
-    for (int k = 0; k < passes; ++k) {
-      const int e = k * kDma1Threads + t;
-      const int src = e < n8 ? e : n8 - 1;  // surplus lanes re-load the last unit into the buffer's slack
-      u16* dst = s_d16 + (size_t)(k * kDma1Threads + wave * 64) * 8;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(row + src),
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    u16* __restrict__ o = out_b + (size_t)c * P;
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-      __builtin_nontemporal_store(gather8(s_d16, ia[v], ic[v]),
-                                  reinterpret_cast<u4v*>(o + p0 + (long long)v * (kDma1Threads * 8)));
-    __builtin_amdgcn_s_barrier();  // every wave has read the row: the next one may land
-    asm volatile("" ::: "memory");
-  }
-}
-
-template <int V>
-bool launch_group_dma1_b16(const u16* points, const int* idx, u16* out, int B, int C, int N, long long P,
-                           long long obs, hipStream_t s) {
-  const long long per_block = (long long)kDma1Threads * 8 * V;
-  if (P % per_block != 0) return false;
-  const long long chunks = P / per_block;
-  const long long base = 8LL * ((B + 7) / 8) * chunks;
-  int cgroups = 1;
-  while (base * cgroups < 512 && cgroups * 2 <= C) cgroups *= 2;
-  const int c_per_group = (C + cgroups - 1) / cgroups;
-  const long long blocks = base * cgroups;
-  const int n8 = N / 8;
-  const int passes = (n8 + kDma1Threads - 1) / kDma1Threads;
-  const size_t lds = (size_t)passes * kDma1Threads * 16;
-  if (lds > 72 * 1024 || chunks > 0x7fffffLL || blocks > 0x7fffffffLL) return false;
-  static pp::DeviceFlags lds_ok;
-  if (pp::allow_big_lds(group_points_dma1_b16_kernel<V>, 80 * 1024, lds_ok) != hipSuccess) return false;
-  group_points_dma1_b16_kernel<V><<<dim3((unsigned)blocks), dim3(kDma1Threads), lds, s>>>(
-      points, idx, out, B, C, N, P, (int)chunks, passes, cgroups, c_per_group, obs);
-  return true;
-}
-
-// three_interpolate, channel-group form (see three_interpolate_rows_kernel): CG rows of T staged in LDS (2 M bytes
-// each), widened as they are gathered; the canonical chain in fp32 and one rounding.  VEC: M % 8 == 0, N % 4 == 0,
-// points / idx / weight 16-byte and out 8-byte aligned -- 16-byte staging, four n per lane, one 8-byte store per channel
-template <int CG, bool VEC, typename T>
-__global__ __launch_bounds__(1024) void three_interpolate_rows_b16_kernel(const T* __restrict__ points,
-                                                                          const int* __restrict__ idx,
-                                                                          const float* __restrict__ weight,
-                                                                          T* __restrict__ out, int B, int C,
-                                                                          int M, int N) {
-  extern __shared__ __attribute__((aligned(16))) u16 s_i16[];  // [CG][M] of T
-  T* s_rows = reinterpret_cast<T*>(s_i16);
-  const int groups = (C + CG - 1) / CG;
-  const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
-  const int b = x + 8 * (y / groups);
-  if (b >= B) return;
-  const int c0 = (y % groups) * CG;
-  const int nc = min(CG, C - c0);
-  const int t = threadIdx.x;
-  for (int k = 0; k < nc; ++k) {
-    const T* __restrict__ rowp = points + ((size_t)b * C + c0 + k) * M;
-    if constexpr (VEC) {
-      for (int e = t; e < (M >> 3); e += 1024)
-        reinterpret_cast<u4v*>(s_rows + (size_t)k * M)[e] = reinterpret_cast<const u4v*>(rowp)[e];
-    } else {
-      for (int e = t; e < M; e += 1024) s_rows[(size_t)k * M + e] = rowp[e];
-    }
-  }
-  __syncthreads();
-  if constexpr (VEC) {
-    for (int n0 = 4 * t; n0 < N; n0 += 4096) {
-      int ii[12];
-      float ww[12];
-#pragma unroll
-      for (int e = 0; e < 3; ++e) {
-        const pp::i4 q = reinterpret_cast<const pp::i4*>(idx + ((size_t)b * N + n0) * 3)[e];
-        const pp::f4 w = reinterpret_cast<const pp::f4*>(weight + ((size_t)b * N + n0) * 3)[e];
-        ii[4 * e] = q.x; ii[4 * e + 1] = q.y; ii[4 * e + 2] = q.z; ii[4 * e + 3] = q.w;
-        ww[4 * e] = w.x; ww[4 * e + 1] = w.y; ww[4 * e + 2] = w.z; ww[4 * e + 3] = w.w;
-      }
-#pragma unroll
-      for (int k = 0; k < CG; ++k)
-        if (k < nc) {
-          const T* __restrict__ sr = s_rows + (size_t)k * M;
-          T r[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            r[j] = pp::narrow<T>(__builtin_fmaf(ww[3 * j + 2], pp::widen(sr[ii[3 * j + 2]]),
-                                                __builtin_fmaf(ww[3 * j], pp::widen(sr[ii[3 * j]]),
-                                                               ww[3 * j + 1] * pp::widen(sr[ii[3 * j + 1]]))));
-          u2v packed;
-          __builtin_memcpy(&packed, r, 8);
-          *reinterpret_cast<u2v*>(out + ((size_t)b * C + c0 + k) * N + n0) = packed;
-        }
-    }
-  } else {  // no alignment assumed: one n per lane and step, 2-byte stores
-    for (int n = t; n < N; n += 1024) {
-      const int* __restrict__ id = idx + ((size_t)b * N + n) * 3;
-      const float* __restrict__ w = weight + ((size_t)b * N + n) * 3;
-      const int i0 = id[0], i1 = id[1], i2 = id[2];
-      const float w0 = w[0], w1 = w[1], w2 = w[2];
-#pragma unroll
-      for (int k = 0; k < CG; ++k)
-        if (k < nc) {
-          const T* __restrict__ sr = s_rows + (size_t)k * M;
-          out[((size_t)b * C + c0 + k) * N + n] = pp::narrow<T>(
-              __builtin_fmaf(w2, pp::widen(sr[i2]), __builtin_fmaf(w0, pp::widen(sr[i0]), w1 * pp::widen(sr[i1]))));
-        }
-    }
-  }
-}
-
-template <int CG, bool VEC, typename T>
-int launch_three_interpolate_rows_b16(const T* points, const int* idx, const float* weight, T* out, int B, int C,
-                                      int M, int N, hipStream_t s) {
-  static pp::DeviceFlags ok;
-  const hipError_t e = pp::allow_big_lds(three_interpolate_rows_b16_kernel<CG, VEC, T>, 152 * 1024, ok);
-  if (e != hipSuccess) return (int)e;
-  const long long wgs = 8LL * ((B + 7) / 8) * ((C + CG - 1) / CG);
-  if (wgs > 0x7fffffffLL) return PP_EINVAL;
-  three_interpolate_rows_b16_kernel<CG, VEC, T><<<dim3((unsigned)wgs), dim3(1024), (size_t)CG * M * sizeof(T), s>>>(
-      points, idx, weight, out, B, C, M, N);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
-template <typename T>
-int three_interpolate_b16(const T* points, const int* idx, const float* weight, T* out, int B, int C, int M, int N,
-                          void* stream) {
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || N == 0) return PP_OK;
-  if (!points || !idx || !weight || !out || M == 0) return PP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int iv = g_interp_variant;
-  const size_t rowb = (size_t)M * sizeof(T);
-  // the channel-group form on the fp32 form's conditions (3: wherever the rows fit -- tests); 2, the fp32 dispatch's
-  // row-at-a-time form, has no 16-bit twin and takes the global form
-  if (iv != 1 && iv != 2 && rowb <= 152 * 1024 &&
-      (iv == 3 || (N >= 2048 && 8LL * ((B + 7) / 8) * ((C + 3) / 4) >= 256))) {
-    const bool vec = M % 8 == 0 && N % 4 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
-                     (uintptr_t)weight % 16 == 0 && (uintptr_t)out % 8 == 0;
-    const bool cg4 = 4 * rowb <= 64 * 1024 && C >= 4;
-    if (vec) {
-      if (cg4) return launch_three_interpolate_rows_b16<4, true, T>(points, idx, weight, out, B, C, M, N, s);
-      return launch_three_interpolate_rows_b16<1, true, T>(points, idx, weight, out, B, C, M, N, s);
-    }
-    if (cg4) return launch_three_interpolate_rows_b16<4, false, T>(points, idx, weight, out, B, C, M, N, s);
-    return launch_three_interpolate_rows_b16<1, false, T>(points, idx, weight, out, B, C, M, N, s);
-  }
-  const long long cols = (N + 255) / 256;
-  const int cpb = pick_c_per_block(cols, B, C);
-  const long long gy = (C + cpb - 1) / cpb;
-  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  three_interpolate_kernel<T><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0, s>>>(
-      points, idx, weight, out, C, M, N, cpb);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
-}  // namespace
-
-extern "C" int pp_gather_forward_b16(const void* points_, const int* idx, void* out_, int B, int C, int N, int M,
-                                     void* stream) {
-  const u16* points = (const u16*)points_;
-  u16* out = (u16*)out_;
-  if (B < 0 || C < 0 || N < 0 || M < 0) return PP_EINVAL;
-  if (B == 0 || C == 0 || M == 0) return PP_OK;
-  if (!points || !idx || !out || N == 0) return PP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int gv = g_gather_variant;
-  // LDS-staged rows on the fp32 form's conditions (2: wherever the row fits -- tests)
-  if (gv != 1 && (size_t)N * 2 <= 152 * 1024 &&
-      (gv == 2 || ((long long)N <= 16LL * M && (long long)B * C >= 512 && M >= 1024))) {
-    const bool vec = N % 8 == 0 && M % 8 == 0 && (uintptr_t)points % 16 == 0 && (uintptr_t)idx % 16 == 0 &&
-                     (uintptr_t)out % 16 == 0;
-    int cpb = 4;
-    while (cpb > 1 && 8LL * ((B + 7) / 8) * ((C + cpb - 1) / cpb) < 1024) cpb /= 2;
-    const int groups = (C + cpb - 1) / cpb;
-    const long long wgs = 8LL * ((B + 7) / 8) * groups;
-    if (wgs <= 0x7fffffffLL) {
-      static pp::DeviceFlags okv, oks;
-      if (vec) {
-        if (pp::allow_big_lds(gather_fwd_lds_b16_kernel<true>, 152 * 1024, okv) != hipSuccess) return PP_EINVAL;
-        gather_fwd_lds_b16_kernel<true><<<dim3((unsigned)wgs), dim3(1024), (size_t)N * 2, s>>>(points, idx, out, B, C,
-                                                                                               N, M, cpb, groups);
-      } else {
-        if (pp::allow_big_lds(gather_fwd_lds_b16_kernel<false>, 152 * 1024, oks) != hipSuccess) return PP_EINVAL;
-        gather_fwd_lds_b16_kernel<false><<<dim3((unsigned)wgs), dim3(1024), (size_t)N * 2, s>>>(points, idx, out, B, C,
-                                                                                                N, M, cpb, groups);
-      }
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
-    }
-  }
-  const long long cols = (M + 255) / 256;
-  const int cpb = pick_c_per_block(cols, B, C);
-  const long long gy = (C + cpb - 1) / cpb;
-  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  gather_fwd_kernel<u16><<<dim3((unsigned)cols, (unsigned)gy, (unsigned)B), dim3(256), 0, s>>>(points, idx, out, C, N,
-                                                                                               M, cpb);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
-extern "C" int pp_group_points_strided_b16(const void* points_, const int* idx, void* out_, int B, int C, int N,
-                                           int npoint, int nsample, long long out_batch_stride, void* stream) {
-  const u16* points = (const u16*)points_;
-  u16* out = (u16*)out_;
-  if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0) return PP_EINVAL;
-  const long long P = (long long)npoint * nsample;
-  const long long obs = out_batch_stride;
-  if (obs < (long long)C * P) return PP_EINVAL;
-  if (B == 0 || C == 0 || P == 0) return PP_OK;
-  if (!points || !idx || !out || N == 0) return PP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec8 = (P % 8 == 0) && (obs % 8 == 0) && ((uintptr_t)idx % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  const int gv = g_group_variant;
-  // LDS-staged forms, on the fp32 dispatch's conditions: the row (2 N bytes) within 64 KiB, rows 16-byte aligned, enough
-  // channels and positions (a knob value that names an LDS form takes it below that size too: tests)
-  if (gv != 1 && vec8 && N % 8 == 0 && (uintptr_t)points % 16 == 0 && (size_t)N * 2 <= 64 * 1024 && C >= 4 &&
-      (gv != 0 || (long long)B * P >= 256LL * 2048)) {
-    // the LDS-DMA form wherever the positions fill whole chunks of 32768, 16384 or 8192 (the fp32 form's chunks:
-    // 8 / 4 / 2 index octets per thread for its 16 / 8 / 4 quads)
-    bool ok = false;
-    if (gv == 616 || gv == 0) ok = launch_group_dma1_b16<8>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 608 || gv == 0)) ok = launch_group_dma1_b16<4>(points, idx, out, B, C, N, P, obs, s);
-    if (!ok && (gv == 604 || gv == 0)) ok = launch_group_dma1_b16<2>(points, idx, out, B, C, N, P, obs, s);
-    if (ok) {
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
-    }
-    // ragged chunks, or forced by 2 / 4 / 8 / a value above 100: the register-staged form (one instantiation)
-    constexpr int V = 4;
-    const long long chunks = (P + 512LL * 8 * V - 1) / (512LL * 8 * V);
-    const long long blocks = 8LL * ((B + 7) / 8) * chunks;
-    if (chunks <= 0x7fffffLL && blocks <= 0x7fffffffLL) {
-      group_points_lds_b16_kernel<V><<<dim3((unsigned)blocks), dim3(512), (size_t)N * 2, s>>>(points, idx, out, B, C, N,
-                                                                                            P, (int)chunks, obs);
-      PP_RETURN_IF_LAUNCH_FAILED();
-      return PP_OK;
-    }
-  }
-  const long long threads = vec8 ? P / 8 : P;
-  const long long cols = (threads + 255) / 256;
-  const int cpb = pick_c_per_block(cols, B, C);
-  const long long gy = (C + cpb - 1) / cpb;
-  if (!grid_ok(cols, gy, B)) return PP_EINVAL;
-  const dim3 grid((unsigned)cols, (unsigned)gy, (unsigned)B);
-  if (vec8)
-    group_points_b16_kernel<true><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
-  else
-    group_points_b16_kernel<false><<<grid, dim3(256), 0, s>>>(points, idx, out, C, N, P, cpb, obs);
-  PP_RETURN_IF_LAUNCH_FAILED();
-  return PP_OK;
-}
-
-extern "C" int pp_three_interpolate_f16(const void* points, const int* idx, const float* weight, void* out, int B,
-                                        int C, int M, int N, void* stream) {
-  return three_interpolate_b16((const pp::f16*)points, idx, weight, (pp::f16*)out, B, C, M, N, stream);
-}
-extern "C" int pp_three_interpolate_bf16(const void* points, const int* idx, const float* weight, void* out, int B,
-                                         int C, int M, int N, void* stream) {
-  return three_interpolate_b16((const pp::bf16*)points, idx, weight, (pp::bf16*)out, B, C, M, N, stream);
-}

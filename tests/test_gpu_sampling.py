@@ -911,9 +911,14 @@ def test_three_interpolate_forward_backward(cuda):
 @pytest.mark.parametrize("variant", [0, 1, 2])
 @pytest.mark.parametrize("b,c,m,n", [(9, 16, 4096, 16384), (2, 7, 1000, 70000), (3, 5, 16384, 40000), (1, 64, 512, 131072),
                                      (17, 130, 2048, 4096), (32, 67, 4096, 8192), (9, 40, 4095, 16383), (8, 36, 4099, 16384),
-                                     (3, 90, 20000, 9000), (5, 70, 30001, 4097)])
+                                     (3, 90, 20000, 9000), (5, 70, 30001, 4097),
+                                     # the smallest shapes that take the channel-group form's other instantiations:
+                                     # <4, unaligned>, <2, aligned>, <2, unaligned>, <1, aligned>, <1, unaligned>
+                                     (1, 125, 7, 2049), (1, 125, 4100, 2048), (1, 125, 4101, 2049),
+                                     (1, 125, 19460, 2048), (1, 125, 19461, 2049)])
 def test_three_interpolate_both_kernels(cuda, variant, b, c, m, n):
-    """channel-group (0, where it applies), global-gather (1) and row-at-a-time LDS (2) forms == oracle
+    """channel-group (0, where it applies: from 2048 points and 256 workgroups, 8 ceil(b / 8) ceil(c / 4); four rows
+    within 64 KiB, else two within 152 KiB, else one), global-gather (1) and row-at-a-time LDS (2) forms == oracle
     bitwise (canonical fma order)."""
     import ctypes
     from pytorch_points_amd import _lib
